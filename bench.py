@@ -24,7 +24,12 @@ The library parks at most 8 GiB of device memory between calls by default; this 
 `config.sample_workers` say how the library scheduled the timed steps.  per_rank_ms_per_step / per_rank_render_ms_per_step: every
 rank's wall time per step and the part of it inside render() (the rest: the one collective per step + waiting for the slowest rank).
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, config, per-rank times,
+scene_build_ms, collective).  `--dump-outputs DIR` writes what the last timed step returned -- the image and every gradient
+tensor, float32, DIR/<name>.npy, at most 64 MiB in all -- so that two builds can be compared output for output (same arguments,
+same inputs and seeds).  `--full` adds everything below, untimed, after the timed steps (the --no-* options leave parts out).
+
+Extra objects in the JSON line (--full):
   roofline      -- the closest-hit traversal kernel by SURVEY.md section 8d: algorithmic bytes (40 B per ray +
                    32 B per node record + 36 B per triangle tested, counted per SAMPLE by the instrumented kernel in an
                    untimed pass; the timed region's bytes = bytes per sample x its samples) / the time during which at
@@ -37,8 +42,8 @@ Extra objects in the JSON line:
                    issue, HBM bytes/s against 8 TB/s).
   roofline_large-- the same kernel on a hierarchy that does not fit the L2 (bunny tessellated to 3.7 M triangles), forward
                    render, + three counter passes: what the design does when traversal goes to the MALL / HBM.
-  collective / sharded_check -- when a process group exists: the one all_gather per step (backend, bytes, ms), and the
-                   gathered sum of one sample per rank against the same blocks rendered on rank 0 (bit-identical).
+  sharded_check -- when a process group exists (`collective`, in every run: the one all_gather per step, backend, bytes,
+                   ms): the gathered sum of one sample per rank against the same blocks rendered on rank 0 (bit-identical).
   cpu_baseline  -- the reference's own C++ core (oracle/_ref, Embree stand-in) on this box's host
                    cores, on bounded samples of the same workload (rank 0, N = 1 only); `gpu_vs_reference`: the full frame
                    at 1 spp rendered by both and compared (image + every gradient tensor).
@@ -94,6 +99,8 @@ class Prepared:
         self.d_img = torch.ones(self.h, self.w, 3, device=device)      # d(sum(img))/d(img)
         self.d_scene, grads = RenderFunction.create_gradient_buffers(self.meta, self.tensors)
         self.grads = [g for g in grads if g is not None]
+        names = gradient_names(self.meta)
+        self.grad_names = ['grad_' + names.get(i, 'arg%d' % i) for i, g in enumerate(grads) if g is not None]
         self.seed = seed
 
     def step(self, i):
@@ -106,6 +113,58 @@ class Prepared:
         u.options.seed = self.seed + i + 1000003
         rd.render(u.scene, u.options, rd.float_ptr(0), rd.float_ptr(self.d_img.data_ptr()), self.d_scene,
                   rd.float_ptr(0), rd.float_ptr(0))
+
+
+def gradient_names(meta):
+    """tensor-argument index -> the input a gradient buffer belongs to (the slots RenderFunction.create_gradient_buffers fills)"""
+    names = {}
+
+    def slot(i, name):
+        if isinstance(i, int) and i >= 0:
+            names.setdefault(i, name)
+    for k, i in meta['camera'].items():
+        if k in ('position', 'look_at', 'up', 'cam_to_world', 'world_to_cam', 'intrinsic_mat_inv', 'intrinsic_mat', 'distortion_params'):
+            slot(i, 'camera_' + k)
+    for s, sm in enumerate(meta['shapes']):
+        for k in ('vertices', 'uvs', 'normals', 'colors'):
+            slot(sm[k], 'shape%d_%s' % (s, k))
+    for m, mm in enumerate(meta['materials']):
+        for k, tm in mm.items():
+            if isinstance(tm, dict):
+                for lv, i in enumerate(tm['levels']):
+                    slot(i, 'material%d_%s_level%d' % (m, k, lv))
+                slot(tm['uv_scale'], 'material%d_%s_uv_scale' % (m, k))
+    for j, lm in enumerate(meta['lights']):
+        slot(lm['intensity'], 'light%d_intensity' % j)
+    em = meta['envmap']
+    if em is not None:
+        for lv, i in enumerate(em['levels']):
+            slot(i, 'envmap_level%d' % lv)
+        slot(em['uv_scale'], 'envmap_uv_scale')
+        slot(em['world_to_env'], 'envmap_world_to_env')
+    return names
+
+
+DUMP_CAP_BYTES = 64 * 2 ** 20     # --dump-outputs writes at most this much (.npy headers included)
+
+
+def dump_outputs(prep, out_dir, cap_bytes=DUMP_CAP_BYTES):
+    """What the timed path returned in its last step -- the image and every gradient tensor -- as out_dir/<name>.npy (float32).
+    An array that does not fit its share of the cap is written as a fixed, seeded sample of its flattened elements (the same
+    indices in every run: sorted, drawn by numpy's default_rng(0) from its size)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = [('image', prep.img)] + list(zip(prep.grad_names, prep.grads))
+    arrays = sorted(((n, t.detach().float().cpu().numpy()) for n, t in arrays), key=lambda nx: nx[1].nbytes)
+    budget = cap_bytes - 256 * len(arrays)              # room for the .npy headers
+    for k, (name, x) in enumerate(arrays):
+        share = budget // (len(arrays) - k)             # smallest first: what a small array leaves goes to the larger ones
+        if x.nbytes > share:
+            keep = share // x.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=keep, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(x, dtype=np.float32))
+        budget -= x.nbytes
 
 
 def trace_stats(reset=False):
@@ -549,6 +608,11 @@ def main():
     ap.add_argument('--res', type=int, default=1024)
     ap.add_argument('--max-bounces', type=int, default=None)
     ap.add_argument('--workload', default='bunny_box', choices=['bunny_box', 'living_room_standin', 'living_room_standin_envmap'])
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the image and every gradient tensor of the last step as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: roofline (instrumented and counter passes, '
+                         'large hierarchy), sharded_check, self_check, cpu_baseline; the --no-* options below apply to these')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-self-check', action='store_true', help='skip the untimed sample-block self-check')
     ap.add_argument('--no-alone-leg', action='store_true', help='skip the extra single-stream step behind roofline.alone')
@@ -558,6 +622,8 @@ def main():
     ap.add_argument('--no-large-leg', action='store_true', help='skip the untimed large-hierarchy traversal leg behind roofline_large')
     ap.add_argument('--cpu-baseline-leg', action='store_true', help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
     if a.max_bounces is None:
         a.max_bounces = 6 if a.workload.startswith('living_room_standin') else 4
     if a.inner:
@@ -644,8 +710,9 @@ def main():
     for i in range(a.warmup):
         prep.step(i)
         reduce_all()
-    lib.rdr_trace_stats_enable(1, 0)
-    trace_stats(reset=True)
+    if a.full:                        # HIP events around the closest-hit launches of the timed steps: `roofline`
+        lib.rdr_trace_stats_enable(1, 0)
+        trace_stats(reset=True)
     dbg0 = _capi.DebugCounters()
     lib.rdr_debug_counters_get(ctypes.byref(dbg0))
     if world > 1:
@@ -662,7 +729,7 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.time() - t0
-    st = trace_stats()
+    st = trace_stats() if a.full else None
     per_rank_ms = [dt / a.steps * 1e3]
     if world > 1:
         # every rank's own clock around the same K steps (they end at the same barrier: what differs is where a rank waited --
@@ -680,7 +747,47 @@ def main():
     timed_batch, timed_workers = int(dbg.last_batch_samples), int(dbg.last_workers)      # how the library scheduled the timed steps
     timed_mallocs = int(dbg.device_mallocs) - int(dbg0.device_mallocs)                  # hipMalloc calls inside the timed region (0: everything came from the buffer cache)
 
-    # untimed, world > 1 (or the forced one-rank collective): the north star's rule "bit-identical sum at 1 vs N GPUs", checked
+    out = None
+    if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(prep, a.dump_outputs)          # the gathered sum when world > 1: the same on every rank
+        out = {
+            'metric': 'Msamples/s fwd+bwd', 'value': value, 'unit': 'Msamples/s', 'n_gpus': world,
+            'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': dt / a.steps * 1e3, 'higher_is_better': True,
+            'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': '%s %dx%d, max_bounces %d, Sobol, %d spp fwd+bwd per step (%s gradients, primary+secondary '
+                                   'edge sampling), sharded by sample index over %d GPU(s): %d spp per GPU'
+                                   % (a.workload, a.res, a.res, a.max_bounces, a.spp,
+                                      'camera-pose' if a.workload.startswith('living_room_standin') else 'vertex', world, spp_rank),
+                       'resolution': [a.res, a.res], 'spp': a.spp, 'spp_per_gpu': spp_rank, 'max_bounces': a.max_bounces,
+                       'parallelism': 'sample-sharded x%d' % world, 'world_size': world, 'pool_cap_mb': pool_cap_mb,
+                       'samples_per_launch': timed_batch, 'sample_workers': timed_workers, 'device_mallocs_in_timed_region': timed_mallocs,
+                       'schedule': os.environ.get('RDR_BENCH_SCHEDULE_NOTE', 'library default: two sample workers, batches as large as the buffer cache holds')},
+            # per rank: wall time per step, and the part of it spent inside render() (the rest: the one collective + waiting
+            # for the slowest rank) -- so that a scaling curve explains itself
+            'per_rank_ms_per_step': per_rank_ms,
+            'per_rank_render_ms_per_step': per_rank_render_ms if world > 1 else [render_s[0] / max(a.steps, 1) * 1e3],
+            # Scene incl. its edge structures, synchronised (the library builds those beside the caller: a render loop does not
+            # wait here)
+            'scene_build_ms': prep.scene_build_s * 1e3,
+            # the one collective per step (image + every gradient tensor in one bucket): which backend carried it, how long a
+            # call took on rank 0 (incl. waiting for the slowest rank); null when no process group exists (plain N = 1 run)
+            'collective': ({'backend': dist.get_backend(), 'world_size': world, 'forced_at_world_1': forced, 'calls': coll['calls'],
+                            'bytes_per_rank_per_call': coll['bytes_per_call'],
+                            'ms_per_call': coll['seconds'] / max(coll['calls'], 1) * 1e3,
+                            'bit_identical_to_local': coll['bit_identical_to_local']} if dist.is_initialized() else None),
+            'full': a.full,
+        }
+    if not a.full:
+        if out is not None:
+            print(json.dumps(out), flush=True)
+        if dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below is untimed ----------------------------------------------------------------------------
+    # world > 1 (or the forced one-rank collective): the north star's rule "bit-identical sum at 1 vs N GPUs", checked
     # on the hardware the job ran on -- a short job of one sample per rank, gathered and summed as in the timed steps, against
     # rank 0 rendering the same `world` sample blocks itself and summing them in rank order (must be equal BIT FOR BIT: image
     # and every gradient tensor), and against one plain call of `world` samples (fp32 summation order: ~1e-7)
@@ -760,7 +867,6 @@ def main():
         lib.rdr_trace_stats_enable(0, 0)
     del short
 
-    out = None
     if rank == 0:
         # Accounting is per SAMPLE, not per launch: the instrumented pass counts the records of the short job exactly; a sample of
         # the timed job draws the same kind of rays, so the timed region's algorithmic bytes are bytes-per-sample x its samples --
@@ -796,32 +902,10 @@ def main():
         if isinstance(prof, dict):
             cands = [prof[k] for k in ('trace_closest_refill', 'trace_closest') if k in prof]
             tc = max(cands, key=lambda v: v['launches_per_sample'] * v['mean_launch_ms_alone']) if cands else None
-        out = {
-            'metric': 'Msamples/s fwd+bwd', 'value': value, 'unit': 'Msamples/s', 'n_gpus': world,
-            'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': dt / a.steps * 1e3, 'higher_is_better': True,
-            'scaling': 'strong', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': '%s %dx%d, max_bounces %d, Sobol, %d spp fwd+bwd per step (%s gradients, primary+secondary '
-                                   'edge sampling), sharded by sample index over %d GPU(s): %d spp per GPU'
-                                   % (a.workload, a.res, a.res, a.max_bounces, a.spp,
-                                      'camera-pose' if a.workload.startswith('living_room_standin') else 'vertex', world, spp_rank),
-                       'resolution': [a.res, a.res], 'spp': a.spp, 'spp_per_gpu': spp_rank, 'max_bounces': a.max_bounces,
-                       'parallelism': 'sample-sharded x%d' % world, 'world_size': world, 'pool_cap_mb': pool_cap_mb,
-                       'samples_per_launch': timed_batch, 'sample_workers': timed_workers, 'device_mallocs_in_timed_region': timed_mallocs,
-                       'schedule': os.environ.get('RDR_BENCH_SCHEDULE_NOTE', 'library default: two sample workers, batches as large as the buffer cache holds')},
-            # per rank: wall time per step, and the part of it spent inside render() (the rest: the one collective + waiting
-            # for the slowest rank) -- so that a scaling curve explains itself
-            'per_rank_ms_per_step': per_rank_ms,
-            'per_rank_render_ms_per_step': per_rank_render_ms if world > 1 else [render_s[0] / max(a.steps, 1) * 1e3],
-            # Scene incl. its edge structures, synchronised (the library builds those beside the caller: a render loop does not
-            # wait here); first Scene of the process / a later one with the same connectivity
-            'scene_build_ms': prep.scene_build_s * 1e3, 'scene_build_warm_ms': scene_build_warm_ms,
-            # the one collective per step (image + every gradient tensor in one bucket): which backend carried it, how long a
-            # call took on rank 0 (incl. waiting for the slowest rank); null when no process group exists (plain N = 1 run)
+        out.update({
+            # first Scene of the process (scene_build_ms) / a later one with the same connectivity
+            'scene_build_warm_ms': scene_build_warm_ms,
             'sharded_check': sharded_check,
-            'collective': ({'backend': dist.get_backend(), 'world_size': world, 'forced_at_world_1': forced, 'calls': coll['calls'],
-                            'bytes_per_rank_per_call': coll['bytes_per_call'],
-                            'ms_per_call': coll['seconds'] / max(coll['calls'], 1) * 1e3,
-                            'bit_identical_to_local': coll['bit_identical_to_local']} if dist.is_initialized() else None),
             'roofline': {'kernel': 'closest-hit traversal (trace_kernel / trace_refill_kernel, all closest-hit launches of the timed region)', 'bound': 'hbm', 'achieved': achieved,
                          'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
                          'traffic': tc['hbm_bytes_per_launch'] if tc else None,
@@ -848,7 +932,7 @@ def main():
                          'note': 'frac = algorithmic bytes (SURVEY.md 8d) over launch time: the 1 MB hierarchy is L2-resident, '
                                  'so this is an L2-served rate; hbm_frac_measured is what reaches HBM (counters), and the '
                                  'kernels are bound by vector-ALU issue at valu_lane_util (DESIGN.md section 3)'},
-        }
+        })
         # the same closest-hit kernel on a hierarchy that does NOT fit the L2 (bunny tessellated to 3.7 M triangles, ~250 MB of records):
         # what the design does when traversal really goes to the MALL / HBM
         if world == 1 and not a.no_large_leg and a.workload == 'bunny_box':

@@ -1,7 +1,8 @@
-"""Drop-in check: the reference's UNMODIFIED Python package (pyredner/render_pytorch.py) drives
-our `redner` module.  Runs only where the reference checkout is mounted (the build container); the
-host debugging harness stands in for the GPU so the whole RenderFunction forward+backward path of
-pyredner is exercised and compared with the oracle."""
+"""Drop-in check: the reference's UNMODIFIED Python package (pyredner/render_pytorch.py, staged by
+oracle/Makefile into the untracked oracle/_ref/pyref/ together with the scene files it reads) drives
+our `redner` module.  Runs only where build() staged it; the host debugging harness stands in for
+the GPU so the whole RenderFunction forward+backward path of pyredner is exercised and compared with
+the oracle."""
 import os
 import subprocess
 import sys
@@ -9,11 +10,12 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
+PYREF = os.path.join(ROOT, 'oracle', '_ref', 'pyref')
+STAGED = 'oracle/_ref/pyref not staged (make -C oracle)'
 
 SCRIPT = r'''
 import sys
-sys.path[:0] = [%(root)r, %(root)r + '/tests', %(root)r + '/oracle/pystubs', %(ref)r]
+sys.path[:0] = [%(root)r, %(root)r + '/tests', %(root)r + '/oracle/pystubs', %(pyref)r]
 import numpy as np, torch
 which = sys.argv[1]
 if which == 'mine':
@@ -42,12 +44,12 @@ np.savez(sys.argv[2], image=img.detach().numpy(), grad=tri.vertices.grad.numpy()
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'pyredner')), reason='reference checkout not mounted')
+@pytest.mark.skipif(not os.path.isfile(os.path.join(PYREF, 'pyredner', 'render_pytorch.py')), reason=STAGED)
 def test_unmodified_pyredner_runs_on_our_redner(hostsim_backend, tmp_path):
     import numpy as np
     from conftest import HOSTSIM_LIB
     script = tmp_path / 'dropin.py'
-    script.write_text(SCRIPT % {'root': ROOT, 'ref': REF, 'lib': HOSTSIM_LIB})
+    script.write_text(SCRIPT % {'root': ROOT, 'pyref': PYREF, 'lib': HOSTSIM_LIB})
     outs = {}
     for which in ('mine', 'oracle'):
         out = str(tmp_path / (which + '.npz'))
@@ -62,7 +64,7 @@ def test_unmodified_pyredner_runs_on_our_redner(hostsim_backend, tmp_path):
 # ---- the reference's own tests/test_bunny_box.py recipe: load_mitsuba -> serialize -> render -> backward ------------
 BUNNY_SCRIPT = r'''
 import os, sys
-sys.path[:0] = [%(root)r, %(root)r + '/tests', %(root)r + '/oracle/pystubs', %(ref)r]
+sys.path[:0] = [%(root)r, %(root)r + '/tests', %(root)r + '/oracle/pystubs', %(pyref)r]
 import numpy as np, torch
 which = sys.argv[1]
 if which == 'mine':
@@ -75,7 +77,7 @@ else:
     sys.modules['redner'] = oracle_util.load_oracle()
 import redner, pyredner
 pyredner.set_use_gpu(False)
-os.chdir(%(ref)r + '/tests')
+os.chdir(%(pyref)r)
 scene = pyredner.load_mitsuba('scenes/bunny_box.xml')          # goes through redner.load_serialized
 scene.shapes[-1].vertices.requires_grad = True
 scene.camera.resolution = (24, 24)
@@ -87,12 +89,12 @@ np.savez(sys.argv[2], image=img.detach().numpy(), grad=scene.shapes[-1].vertices
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'pyredner')), reason='reference checkout not mounted')
+@pytest.mark.skipif(not os.path.isfile(os.path.join(PYREF, 'pyredner', 'render_pytorch.py')), reason=STAGED)
 def test_load_mitsuba_bunny_box_on_our_redner(hostsim_backend, tmp_path):
     import numpy as np
     from conftest import HOSTSIM_LIB
     script = tmp_path / 'dropin_bunny.py'
-    script.write_text(BUNNY_SCRIPT % {'root': ROOT, 'ref': REF, 'lib': HOSTSIM_LIB})
+    script.write_text(BUNNY_SCRIPT % {'root': ROOT, 'pyref': PYREF, 'lib': HOSTSIM_LIB})
     outs = {}
     for which in ('mine', 'oracle'):
         out = str(tmp_path / (which + '.npz'))
@@ -104,7 +106,7 @@ def test_load_mitsuba_bunny_box_on_our_redner(hostsim_backend, tmp_path):
     assert rel < 1e-4, rel
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, 'tests/scenes/teapot.serialized')), reason='reference checkout not mounted')
+@pytest.mark.skipif(not os.path.isfile(os.path.join(PYREF, 'scenes', 'teapot_specular.serialized')), reason=STAGED)
 def test_load_serialized_equals_reference():
     """redner.load_serialized (zlib + numpy) vs the reference's C++ loader (src/load_serialized.cpp) on every sub-mesh."""
     import numpy as np
@@ -112,7 +114,7 @@ def test_load_serialized_equals_reference():
     from redner_amd import redner
     ref = oracle_util.load_oracle()
     for fn, n in (('bunny_box.serialized', 7), ('teapot.serialized', 6), ('teapot_specular.serialized', 7)):
-        path = os.path.join(REF, 'tests/scenes', fn)
+        path = os.path.join(PYREF, 'scenes', fn)
         for i in range(n):
             a, b = redner.load_serialized(path, i), ref.load_serialized(path, i)
             for name in ('vertices', 'indices', 'uvs', 'normals'):

@@ -9,7 +9,7 @@ gathered, summed in fixed rank order, unpacked.  The sum of one part is the part
  * `render_sharded` (the autograd surface) in a one-rank nccl group against the plain RenderFunction in the same process;
  * an 8-rank rehearsal of the driver's 8-GPU command on the one GPU (gloo: RCCL refuses two ranks on one device), 8 x 2 spp of
    the benchmark frame: the self-launch, per-rank device binding, per-rank pool / thread caps at the real world size, and
-   bench.py's own `sharded_check` (gathered image == the same 8 blocks rendered on one device, bit for bit).
+   bench.py's own `sharded_check` (gathered image == the same 8 blocks rendered on one device, bit for bit; `--full`).
 
 With RDR_RCCL_LOG=<dir> the NCCL_DEBUG=INFO output of the first two is kept (profiles/r6_rccl_one_rank.log)."""
 import json
@@ -59,7 +59,7 @@ def test_bench_one_rank_under_launcher_runs_the_collective_over_rccl():
     env = _clean_env(REDNER_AMD_FORCE_COLLECTIVE='1', NCCL_DEBUG='INFO', NCCL_DEBUG_SUBSYS='INIT,COLL')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--spp', '32', '--steps', '1',
-           '--warmup', '0', '--no-profile', '--no-cpu-baseline', '--no-self-check', '--no-alone-leg']
+           '--warmup', '0', '--full', '--no-profile', '--no-cpu-baseline', '--no-self-check', '--no-alone-leg']
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     _keep_log('bench_one_rank_nccl.log', ' '.join(cmd) + '\n--- stdout\n' + r.stdout + '\n--- stderr\n' + r.stderr)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -155,7 +155,7 @@ def test_eight_rank_rehearsal_on_one_gpu():
         pytest.skip('needs ~60 GB of free device memory for 8 ranks on one GPU')
     env = _clean_env(RDR_BENCH_SHARE_GPU='1')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--spp', '16', '--steps', '1', '--warmup', '0',
-                        '--no-profile', '--no-cpu-baseline', '--no-self-check', '--no-alone-leg'], env=env, timeout=1500,
+                        '--full', '--no-profile', '--no-cpu-baseline', '--no-self-check', '--no-alone-leg'], env=env, timeout=1500,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     _keep_log('bench_eight_ranks_shared_gpu.log', r.stdout + '\n--- stderr\n' + r.stderr[-20000:])
     assert r.returncode == 0, r.stderr[-3000:]

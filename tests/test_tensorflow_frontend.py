@@ -222,10 +222,11 @@ def test_tensorflow_surface_gpu(gpu_backend, name, res, spp, bounces, kind):
     _compare(img, timg, grads, exact=False)
 
 
-REF_TF = '/root/reference/pyredner_tensorflow'
+# the reference's package, staged by oracle/Makefile into the untracked oracle/_ref/pyref/
+REF_TF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'oracle', '_ref', 'pyref', 'pyredner_tensorflow')
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_TF), reason='no reference checkout (only in the build container)')
+@pytest.mark.skipif(not os.path.isdir(REF_TF), reason='oracle/_ref/pyref not staged (make -C oracle)')
 def test_dropin_serves_the_reference_tensorflow_package():
     """The other way to TensorFlow: the reference's own `pyredner_tensorflow` over the drop-in `redner` module
     (redner_amd.install()).  It cannot be imported here (no TensorFlow, and its data_ptr op is compiled against one), so

@@ -6,10 +6,10 @@ export RDR_PARITY_REPORT=$OUT/parity_report.jsonl
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $OUT/pytest.log
 unset RDR_PARITY_REPORT
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log
-timeout 900 python bench.py 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json
-[ -n "$FINAL_WITH_ONE_SAMPLE" ] && RDR_BATCH=1 timeout 600 python bench.py --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_one_sample_per_launch.json
-timeout 600 python bench.py --workload living_room_standin --spp 32 --steps 2 --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_living_room_standin.json
-timeout 600 python bench.py --workload living_room_standin_envmap --spp 32 --steps 2 --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_living_room_standin_envmap.json
+timeout 900 python bench.py --full 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json
+[ -n "$FINAL_WITH_ONE_SAMPLE" ] && RDR_BATCH=1 timeout 600 python bench.py --full --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_one_sample_per_launch.json
+timeout 600 python bench.py --full --workload living_room_standin --spp 32 --steps 2 --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_living_room_standin.json
+timeout 600 python bench.py --full --workload living_room_standin_envmap --spp 32 --steps 2 --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_living_room_standin_envmap.json
 { for cfg in "256 4" "256 4 move" "256 16" "128 8" "512 4" "64 4"; do echo "== $cfg"; python tools/small_loop_timing.py $cfg 2>&1 | tail -4; done; echo "== 256 4, one sample per launch (RDR_BATCH=1)"; RDR_BATCH=1 python tools/small_loop_timing.py 256 4 2>&1 | tail -4; } > $OUT/small_loop.txt
 cd /tmp && export TMPDIR=/tmp
 P="python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --spp 16 --no-cpu-baseline --no-alone-leg --no-profile --no-self-check"

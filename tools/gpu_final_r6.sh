@@ -8,11 +8,11 @@ export RDR_RCCL_LOG=$OUT/rccl
 timeout 1700 python -m pytest tests -m gpu -q --durations=8 -p no:cacheprovider 2>&1 | tail -25 > $OUT/pytest.log
 unset RDR_PARITY_REPORT RDR_RCCL_LOG
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log
-( time timeout 1500 python bench.py 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json ) 2> $OUT/bench_default.time
-timeout 600 python bench.py --workload living_room_standin --spp 64 --steps 2 --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_living_room_standin.json
-timeout 600 python bench.py --workload living_room_standin_envmap --spp 64 --steps 2 --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_living_room_standin_envmap.json
-RDR_POOL_CAP_MB=8192 timeout 600 python bench.py --steps 2 --no-cpu-baseline --no-profile --no-self-check --no-large-leg 2> /dev/null | tail -1 > $OUT/bench_pool_cap_8g.json
-RDR_POOL_CAP_MB=16384 timeout 600 python bench.py --steps 2 --no-cpu-baseline --no-profile --no-self-check --no-large-leg 2> /dev/null | tail -1 > $OUT/bench_pool_cap_16g.json
+( time timeout 1500 python bench.py --full 2> $OUT/bench_default.err | tail -1 > $OUT/bench_default.json ) 2> $OUT/bench_default.time
+timeout 600 python bench.py --full --workload living_room_standin --spp 64 --steps 2 --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_living_room_standin.json
+timeout 600 python bench.py --full --workload living_room_standin_envmap --spp 64 --steps 2 --no-cpu-baseline --no-profile --no-self-check 2> /dev/null | tail -1 > $OUT/bench_living_room_standin_envmap.json
+RDR_POOL_CAP_MB=8192 timeout 600 python bench.py --full --steps 2 --no-cpu-baseline --no-profile --no-self-check --no-large-leg 2> /dev/null | tail -1 > $OUT/bench_pool_cap_8g.json
+RDR_POOL_CAP_MB=16384 timeout 600 python bench.py --full --steps 2 --no-cpu-baseline --no-profile --no-self-check --no-large-leg 2> /dev/null | tail -1 > $OUT/bench_pool_cap_16g.json
 { for cfg in "256 4" "256 4 move" "256 16" "128 8" "512 4"; do echo "== $cfg"; python tools/small_loop_timing.py $cfg 2>&1 | tail -4; done; } > $OUT/small_loop.txt
 { echo "== 256 4 RDR_NO_NEE_COMPACT=1 RDR_PICKH_ONE_LAUNCH=1"; RDR_NO_NEE_COMPACT=1 RDR_PICKH_ONE_LAUNCH=1 python tools/small_loop_timing.py 256 4 2>&1 | tail -4; } >> $OUT/small_loop.txt
 python tools/scene_build_timing.py 2>&1 | tail -3 > $OUT/scene_build.txt

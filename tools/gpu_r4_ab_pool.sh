@@ -1,4 +1,4 @@
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-self-check --no-alone-leg"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-self-check --no-alone-leg"
 show() { python -c "
 import json,sys
 d=json.loads(open('$1').read()); r=d['roofline']

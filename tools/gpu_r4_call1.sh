@@ -8,7 +8,7 @@ timeout 1500 python -m pytest tests -m gpu -q -x --durations=15 2>&1 | tail -40 
 unset RDR_PARITY_REPORT
 cat $OUT/pytest.log | tail -30
 python tools/parked_bytes.py 2>&1 | tail -1 | tee $OUT/parked.txt
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-self-check --no-alone-leg"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-self-check --no-alone-leg"
 show() { python -c "
 import json,sys
 d=json.loads(open('$1').read()); r=d['roofline']

@@ -6,7 +6,7 @@ export RDR_PARITY_REPORT=$OUT/parity_report.jsonl
 timeout 1500 python -m pytest tests -m gpu -q -x --durations=8 2>&1 | tail -25 > $OUT/pytest.log
 unset RDR_PARITY_REPORT
 tail -22 $OUT/pytest.log
-B="python bench.py --steps 2 --warmup 1 --spp 32 --no-cpu-baseline --no-profile --no-self-check --no-alone-leg"
+B="python bench.py --full --steps 2 --warmup 1 --spp 32 --no-cpu-baseline --no-profile --no-self-check --no-alone-leg"
 show() { python -c "
 import json,sys
 d=json.loads(open('$1').read()); r=d['roofline']

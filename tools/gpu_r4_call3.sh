@@ -1,7 +1,7 @@
 #!/bin/bash
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r4_call3
 rm -rf $OUT; mkdir -p $OUT
-B="python bench.py --steps 2 --warmup 1 --spp 32 --no-cpu-baseline --no-profile --no-self-check --no-alone-leg --workload living_room_standin"
+B="python bench.py --full --steps 2 --warmup 1 --spp 32 --no-cpu-baseline --no-profile --no-self-check --no-alone-leg --workload living_room_standin"
 show() { python -c "
 import json,sys
 d=json.loads(open('$1').read()); r=d['roofline']

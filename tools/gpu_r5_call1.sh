@@ -4,7 +4,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/r5_call1
 rm -rf $OUT; mkdir -p $OUT
 timeout 1200 python -m pytest tests/test_dropin_pyredner_gpu.py tests/test_distributed.py tests/test_edge_cases.py tests/test_tuning.py -m gpu -q -x --durations=5 2>&1 | tail -30 > $OUT/pytest_new.log
 cat $OUT/pytest_new.log
-timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-self-check 2> $OUT/bench.err | tail -1 > $OUT/bench_baseline.json
+timeout 900 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-self-check 2> $OUT/bench.err | tail -1 > $OUT/bench_baseline.json
 python - <<'PY'
 import json,os
 d=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/r5_call1/bench_baseline.json').read())

@@ -2,7 +2,7 @@
 # Round 6: the default bench line (as the driver runs it) + the rocprofv3 kernel statistics of the same command (short form).
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r6_h; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-( time python bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err
+( time python bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -3 $OUT/bench_default.err
 python - $OUT/bench_default.json <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 for spec in "one|RDR_PICKH_ONE_LAUNCH=1" "split_k4|X=0" "split_k1|RDR_PICKH_REFILL=1,8,8"; do
   label=${spec%%|*}; envs=${spec#*|}
-  env $envs python bench.py --spp 64 --steps 2 --warmup 1 --no-cpu-baseline --no-self-check 2>/dev/null | tail -1 > $OUT/bench_$label.json
+  env $envs python bench.py --full --spp 64 --steps 2 --warmup 1 --no-cpu-baseline --no-self-check 2>/dev/null | tail -1 > $OUT/bench_$label.json
   python - $OUT/bench_$label.json $label <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); k = d['roofline']['kernels'] or {}
