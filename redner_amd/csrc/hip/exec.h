@@ -52,7 +52,7 @@ __host__ inline void *lds_column_host_stub() { return nullptr; }
 // those lanes in lane order) and issue ONE atomic; that is repeated for up to kAccumRounds distinct
 // addresses (lanes on different materials / walls), whoever is left issues its own hardware fp64 atomic.
 //
-// The accumulators are replicated (GradStore in render.cpp) and a wave adds to the replica its id selects, which spreads
+// The accumulators are replicated (GradStore in grad_store.h) and a wave adds to the replica its id selects, which spreads
 // the atomics on one logical address over many lines / channels.  Two tiers, because the replica count that the memory
 // budget allows depends on the size of what is replicated: SMALL tensors (camera, light intensities, constant albedos,
 // the vertices of low-poly shapes, the top mip levels) are the ones every wave adds to, and get 256 replicas whatever
@@ -66,7 +66,7 @@ struct ReplicaLayout {
 };
 static __device__ ReplicaLayout g_rep = {nullptr, 0, 0, 0, 0};
 // (callers that add a GROUP of consecutive accumulators -- accum_triple, accum_block -- call this for the first address only:
-//  a tensor never straddles hot_end, render.cpp: GradStore checks its layout)
+//  a tensor never straddles hot_end, grad_store.h: GradStore checks its layout)
 __device__ inline double *replica_of(double *p) {
     const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
     const bool hot = p < g_rep.hot_end;
@@ -264,6 +264,7 @@ inline int current_device() { int d = 0; (void)hipGetDevice(&d); return d; }
 // Side streams for stages that do not depend on each other (the edge-pick walks and the bounce adjoint of one path
 // depth): each of them keeps a fraction of the lanes busy and waits on dependent loads, so they fill each other's gaps.
 // StreamScope redirects every launch made inside it; Fence orders two streams (record on the producer, gate the consumer).
+// (render.cpp: Fork puts the two together -- the one way the host driver puts work on a side stream.)
 hipStream_t side_stream(int k);          // trace.hip: two non-blocking streams per device, created on first use
 struct StreamScope {
     hipStream_t saved;
@@ -340,7 +341,7 @@ struct Fence {
     void gate(hipStream_t consumer) { check(hipStreamWaitEvent(consumer, e, 0), "hipStreamWaitEvent"); }
 };
 
-// Replicated gradient accumulators (see GradStore in render.cpp): a power of two, at most 256 and as many as fit `budget`.
+// Replicated gradient accumulators (see GradStore in grad_store.h): a power of two, at most 256 and as many as fit `budget`.
 // Must be called from the translation unit that instantiates the stage kernels.
 inline int choose_replicas(size_t replica_bytes, size_t budget) {
     int r = 256;
@@ -707,7 +708,7 @@ void select_device(int use_gpu, int gpu_index);
 } // namespace exec
 
 namespace rdr {
-// What GradStore (render.cpp) tells its accumulator backend: the small tier has been laid out / a small tensor is about to be
+// What GradStore (grad_store.h) tells its accumulator backend: the small tier has been laid out / a small tensor is about to be
 // folded into the caller's floats / the fold is done.  The fp64 replicas need none of it (tests/hostsim/exec.h keeps the
 // reference's fp32 accumulation order beside them through these three).
 inline void accumulators_laid_out(double *, size_t) {}

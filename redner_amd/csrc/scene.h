@@ -50,7 +50,7 @@ struct Scene {
     bool has_vertex_colors = false;
     bool has_mipmaps = false;
     int emitter_triangles = 0;     // triangles of all area-light shapes together (render.cpp: last-bounce emitter test)
-    bool diffuse_only = false;     // every material: constant specular reflectance (0, 0, 0) -- see render.cpp: run_sample
+    bool diffuse_only = false;     // every material: constant specular reflectance (0, 0, 0) -- see render.cpp: Backward::sweep_depth
     EnvmapD h_envmap;              // valid when d.envmap != nullptr      // some texture has > 1 level, i.e. ray differentials influence results
 
     // host mirrors

@@ -9,7 +9,7 @@
 // reference (src/camera.h:44-65, src/area_light.h:18-20).
 //
 // Gradient targets (G*) are fp64 accumulators owned by the renderer; they are folded into the
-// caller's fp32 gradient tensors once at the end of render() (see render.cpp: flush_gradients).
+// caller's fp32 gradient tensors once at the end of render() (see grad_store.h: GradStore::flush).
 #pragma once
 #include "vecmath.h"
 
