@@ -243,6 +243,36 @@ int rdr_render(const rdr_scene *scene, const rdr_render_options *options,
  * Returns -1 for an unknown channel id. */
 int rdr_compute_num_channels(const int *channels, int num_channels, int max_generic_texture_dimension);
 
+/* Deferred shading of a G-buffer (pyredner/render_utils.py:8-313: the four deferred lights, the loop over them, the
+ * anti-aliasing resolve) and its adjoint, each one pass over the G-buffer (csrc/deferred.h).
+ * The G-buffer is [num_images, height * aa_samples, width * aa_samples, 9 + alpha] fp32: position 3, shading normal 3, diffuse
+ * reflectance 3 and, with alpha, alpha 1.  The image is [num_images, height, width, 3 + alpha]: per texel the sum over the lights
+ * of its image, alpha passed through unshaded, the mean over each aa_samples x aa_samples block.
+ * Lights are rows of one table: light_type[l] and light_params[l][10] = intensity 3, position 3, direction 3 (directional: its
+ * direction; spot: the spot direction), spot exponent 1; entries a type does not use are ignored.  Image n is lit by the lights
+ * [image_light_range[2n], image_light_range[2n+1]).
+ *   ambient      I * a
+ *   point        d = pos - p, l = d / |d|:            I * max(l.n, 0) * (a / pi) / d.d
+ *   directional  l = -dir / |dir|:                    I * max(l.n, 0) * (a / pi)
+ *   spot         l = (pos - p) / |pos - p|, s = -sdir / |sdir|:   I * pow(max(l.s, 0), e) * max(l.n, 0) * (a / pi)
+ * g_buffer, light_params, image, d_* are DEV pointers on device gpu_index (a negative gpu_index: host memory, which only the
+ * CPU debugging harness accepts); with alpha the G-buffers must be 8-byte and the images 16-byte aligned.  The backward call
+ * writes every element of d_g_buffer and d_light_params (no zero-filled buffers needed); the light gradients are summed in a
+ * fixed order: bitwise reproducible from run to run.  Launches are ordered on the rdr_set_stream stream; both calls synchronise
+ * before returning.  Return 0 on success. */
+enum rdr_deferred_light_type { RDR_DL_AMBIENT = 0, RDR_DL_POINT = 1, RDR_DL_DIRECTIONAL = 2, RDR_DL_SPOT = 3 };
+typedef struct rdr_deferred_desc {
+    int num_images, height, width;      /* OUTPUT size */
+    int aa_samples, alpha;
+    int num_lights;
+    const int32_t *light_type;          /* HOST [num_lights] */
+    const int32_t *image_light_range;   /* HOST [num_images][2] */
+    int gpu_index;
+} rdr_deferred_desc;
+int rdr_deferred_shade(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params, float *image);
+int rdr_deferred_shade_backward(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params,
+                                const float *d_image, float *d_g_buffer, float *d_light_params);
+
 /* Message of the last failure on the calling thread ("" if none). */
 const char *rdr_last_error(void);
 

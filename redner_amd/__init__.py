@@ -2,10 +2,24 @@
 
     redner_amd.redner            the `redner` module surface (ctypes over the C ABI)
     redner_amd.render_pytorch    RenderFunction (torch.autograd.Function) + minimal scene classes
+    redner_amd.render_utils      render_deferred + the deferred lights, render_g_buffer / render_albedo /
+                                 render_pathtracing / render_generic; all exported here:
+                                 `from redner_amd import render_deferred, PointLight`
     redner_amd.install()         register redner_amd.redner as `redner` for the reference's
                                  unmodified pyredner package
 """
 import sys
+
+_RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'DeferredShade',
+                 'deferred_shade', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo', 'render_pathtracing')
+
+
+def __getattr__(name):
+    # resolved on first use: `import redner_amd` alone does not import torch
+    if name in _RENDER_UTILS:
+        from . import render_utils
+        return getattr(render_utils, name)
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 
 def install():

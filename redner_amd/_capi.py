@@ -133,11 +133,22 @@ class DebugCounters(C.Structure):
                 ('last_batch_samples', C.c_uint64), ('last_workers', C.c_uint64)]
 
 
+class DeferredDesc(C.Structure):
+    """rdr_deferred_desc (include/redner_amd.h)."""
+    _fields_ = [('num_images', C.c_int), ('height', C.c_int), ('width', C.c_int),
+                ('aa_samples', C.c_int), ('alpha', C.c_int), ('num_lights', C.c_int),
+                ('light_type', c_int_p), ('image_light_range', c_int_p), ('gpu_index', C.c_int)]
+
+
+# rdr_deferred_light_type
+DL_AMBIENT, DL_POINT, DL_DIRECTIONAL, DL_SPOT = range(4)
+
 EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_texture_dimension',
            'rdr_render', 'rdr_compute_num_channels', 'rdr_last_error',
            'rdr_trace_stats_enable', 'rdr_trace_stats_reset', 'rdr_trace_stats_get', 'rdr_scene_trace',
            'rdr_debug_counters_get', 'rdr_trim_cache', 'rdr_debug_dump_edges', 'rdr_debug_bvh_check',
-           'rdr_set_stream', 'rdr_set_pool_cap_mb', 'rdr_get_pool_cap_mb', 'rdr_set_build_flags', 'rdr_debug_libm', 'rdr_libm_exact')
+           'rdr_set_stream', 'rdr_set_pool_cap_mb', 'rdr_get_pool_cap_mb', 'rdr_set_build_flags', 'rdr_debug_libm', 'rdr_libm_exact',
+           'rdr_deferred_shade', 'rdr_deferred_shade_backward')
 
 _lib = None
 _lib_path = None
@@ -198,6 +209,10 @@ def load(path=None):
     lib.rdr_libm_exact.argtypes = []
     lib.rdr_debug_libm.restype = C.c_int
     lib.rdr_debug_libm.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    lib.rdr_deferred_shade.restype = C.c_int
+    lib.rdr_deferred_shade.argtypes = [C.POINTER(DeferredDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rdr_deferred_shade_backward.restype = C.c_int
+    lib.rdr_deferred_shade_backward.argtypes = [C.POINTER(DeferredDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib, _lib_path = lib, path
     return lib
 

@@ -3,6 +3,7 @@
 #include "render.h"
 #include "tuning.h"
 #include "edges.h"
+#include "deferred.h"
 #include <cstdio>
 #include "scene.h"
 #include <cstring>
@@ -93,6 +94,37 @@ int rdr_render(const rdr_scene *scene, const rdr_render_options *options, float 
         exec::select_device(1, s.gpu_index);
         use_caller_stream();
         rdr::render(s, *options, rendered_image, d_rendered_image, d_scene, screen_gradient_image, debug_image);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_deferred_shade(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params, float *image) {
+    try {
+        g_last_error.clear();
+        if (!desc) throw std::runtime_error("rdr_deferred_shade: a description is required");
+        std::lock_guard<std::recursive_mutex> lk(device_lock(desc->gpu_index));
+        exec::select_device(desc->gpu_index >= 0, desc->gpu_index);
+        use_caller_stream();
+        rdr::dfr::shade(*desc, g_buffer, light_params, image);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_deferred_shade_backward(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params,
+                                const float *d_image, float *d_g_buffer, float *d_light_params) {
+    try {
+        g_last_error.clear();
+        if (!desc) throw std::runtime_error("rdr_deferred_shade_backward: a description is required");
+        std::lock_guard<std::recursive_mutex> lk(device_lock(desc->gpu_index));
+        exec::select_device(desc->gpu_index >= 0, desc->gpu_index);
+        use_caller_stream();
+        rdr::dfr::shade_backward(*desc, g_buffer, light_params, d_image, d_g_buffer, d_light_params);
         return 0;
     } catch (const std::exception &e) {
         set_error(e.what());

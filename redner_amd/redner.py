@@ -410,6 +410,50 @@ def render(scene, options, rendered_image, d_rendered_image, d_scene, screen_gra
         raise RuntimeError('redner.render: ' + _capi.last_error())
 
 
+class DeferredLightType(enum.IntEnum):     # rdr_deferred_light_type (not in the reference's module: its deferred lights are torch code)
+    ambient = _capi.DL_AMBIENT
+    point = _capi.DL_POINT
+    directional = _capi.DL_DIRECTIONAL
+    spot = _capi.DL_SPOT
+
+
+def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index):
+    d = _capi.DeferredDesc()
+    d.num_images, d.height, d.width = int(num_images), int(height), int(width)
+    d.aa_samples, d.alpha, d.num_lights = int(aa_samples), int(bool(alpha)), len(light_types)
+    types = (C.c_int32 * max(len(light_types), 1))(*[int(t) for t in light_types])
+    flat = [int(v) for r in image_light_ranges for v in r]
+    if len(flat) != 2 * d.num_images:
+        raise RuntimeError('redner.deferred_shade: %d light ranges for %d images' % (len(image_light_ranges), d.num_images))
+    ranges = (C.c_int32 * max(len(flat), 1))(*flat)
+    d.light_type, d.image_light_range = types, ranges
+    d.gpu_index = int(gpu_index) if use_gpu else -1
+    return d, (types, ranges)
+
+
+def deferred_shade(g_buffer, light_params, image, num_images, height, width, aa_samples, alpha, light_types,
+                   image_light_ranges, use_gpu, gpu_index):
+    """Not in the reference: rdr_deferred_shade (include/redner_amd.h).  g_buffer [N, H * aa, W * aa, 9 + alpha],
+    light_params [L, 10], image [N, H, W, 3 + alpha]: float_ptr; light_types: L DeferredLightType; image_light_ranges: N
+    (begin, end) pairs into the table."""
+    lib = _capi.lib()
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index)
+    _use_torch_stream(lib, use_gpu, gpu_index)
+    if lib.rdr_deferred_shade(C.byref(d), _addr(g_buffer), _addr(light_params), _addr(image)) != 0:
+        raise RuntimeError('redner.deferred_shade: ' + _capi.last_error())
+
+
+def deferred_shade_backward(g_buffer, light_params, d_image, d_g_buffer, d_light_params, num_images, height, width,
+                            aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index):
+    """Not in the reference: rdr_deferred_shade_backward; writes every element of d_g_buffer and d_light_params."""
+    lib = _capi.lib()
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index)
+    _use_torch_stream(lib, use_gpu, gpu_index)
+    if lib.rdr_deferred_shade_backward(C.byref(d), _addr(g_buffer), _addr(light_params), _addr(d_image), _addr(d_g_buffer),
+                                       _addr(d_light_params)) != 0:
+        raise RuntimeError('redner.deferred_shade_backward: ' + _capi.last_error())
+
+
 def _use_torch_stream(lib, use_gpu, gpu_index=None):
     """The library orders its launches on the calling thread's CURRENT torch stream OF THE SCENE'S DEVICE (rdr_set_stream):
     tensors produced under `with torch.cuda.stream(s):` are read after their producers without a device-wide

@@ -1,0 +1,318 @@
+"""Deferred shading and the render_* family on the MI355X-native renderer.
+
+The names, arguments and meaning are those of the reference's `pyredner/render_utils.py`, so a pyredner deferred-shading script
+needs only its import line changed:
+
+    from redner_amd import render_deferred, PointLight, AmbientLight
+
+    img = render_deferred(scene, [AmbientLight(ia), PointLight(pos, ip)], aa_samples=2, seed=1)
+    img.sum().backward()          # gradients reach the scene AND ia, pos, ip
+
+The G-buffer (position, shading normal, diffuse reflectance[, alpha]) comes from `RenderFunction` at `aa_samples` times the
+resolution; the lights, their sum and the anti-aliasing resolve are ONE native kernel (`rdr_deferred_shade`,
+csrc/deferred.h), its adjoint another -- where the reference composes ~15 whole-image torch operations per light.  There is
+no fall-back to torch operations: without the native library the call raises.
+
+Per G-buffer texel with position p, normal n, albedo a, summed over the lights (I: the light's rgb intensity):
+
+    AmbientLight      I * a
+    PointLight        d = pos - p, l = d / |d|:       I * max(l.n, 0) * (a / pi) / d.d
+    DirectionalLight  l = -dir / |dir|:               I * max(l.n, 0) * (a / pi)
+    SpotLight         l = (pos - p) / |pos - p|, s = -sdir / |sdir|:
+                                                      I * pow(max(l.s, 0), e) * max(l.n, 0) * (a / pi)
+
+then alpha appended unshaded and the mean over each aa x aa block.
+"""
+import random
+from typing import List, Optional, Union
+
+import torch
+
+from . import redner as _default_backend
+from .render_pytorch import RenderFunction, Scene
+
+_LIGHT_PARAMS = 10          # csrc/deferred.h: intensity 3, position 3, direction 3, spot exponent 1
+
+
+class DeferredLight:
+    """A light of the deferred pass: a plain holder of tensors (any device; they may require grad)."""
+    light_type = None
+
+    def _pieces(self):
+        """-> (intensity, position | None, direction | None, exponent | None)"""
+        raise NotImplementedError
+
+    def render(self, position: torch.Tensor, normal: torch.Tensor, albedo: torch.Tensor):
+        """This light alone on explicit position / normal / albedo images ([..., 3] each, broadcast against each other),
+        through the same native kernel as render_deferred."""
+        position, normal, albedo = torch.broadcast_tensors(position, normal, albedo)
+        shape = position.shape
+        if len(shape) < 1 or shape[-1] != 3:
+            raise RuntimeError('DeferredLight.render: position, normal and albedo must be [..., 3]')
+        g = torch.cat([position, normal, albedo], dim=-1).to(torch.float32)
+        g = g.reshape(1, 1, -1, 9) if g.dim() < 3 else g.reshape((-1,) + tuple(g.shape[-3:]))
+        img = deferred_shade(g, [self], alpha=False, aa_samples=1)
+        return img.reshape(shape)
+
+
+class AmbientLight(DeferredLight):
+    light_type = _default_backend.DeferredLightType.ambient
+
+    def __init__(self, intensity: torch.Tensor):
+        self.intensity = intensity
+
+    def _pieces(self):
+        return self.intensity, None, None, None
+
+
+class PointLight(DeferredLight):
+    """Point light with squared-distance falloff."""
+    light_type = _default_backend.DeferredLightType.point
+
+    def __init__(self, position: torch.Tensor, intensity: torch.Tensor):
+        self.position, self.intensity = position, intensity
+
+    def _pieces(self):
+        return self.intensity, self.position, None, None
+
+
+class DirectionalLight(DeferredLight):
+    light_type = _default_backend.DeferredLightType.directional
+
+    def __init__(self, direction: torch.Tensor, intensity: torch.Tensor):
+        self.direction, self.intensity = direction, intensity
+
+    def _pieces(self):
+        return self.intensity, None, self.direction, None
+
+
+class SpotLight(DeferredLight):
+    """Spot light with cosine-power falloff and no distance falloff (no cutoff: it would not be differentiable)."""
+    light_type = _default_backend.DeferredLightType.spot
+
+    def __init__(self, position: torch.Tensor, spot_direction: torch.Tensor, spot_exponent: torch.Tensor,
+                 intensity: torch.Tensor):
+        self.position, self.spot_direction = position, spot_direction
+        self.spot_exponent, self.intensity = spot_exponent, intensity
+
+    def _pieces(self):
+        return self.intensity, self.position, self.spot_direction, self.spot_exponent
+
+
+def pack_lights(lights, device):
+    """[L, 10] fp32 table on `device` (layout: csrc/deferred.h) + the L light types.  One cat over the lights' tensors:
+    autograd routes the table's gradient back to them."""
+    sizes = (3, 3, 3, 1)
+    pieces, types = [], []
+    zeros = {n: torch.zeros(n, dtype=torch.float32, device=device) for n in (1, 3)}
+    for light in lights:
+        if not isinstance(light, DeferredLight) or light.light_type is None:
+            raise RuntimeError('render_deferred: %r is not a deferred light' % (light,))
+        types.append(int(light.light_type))
+        for t, n in zip(light._pieces(), sizes):
+            if t is None:
+                pieces.append(zeros[n])
+                continue
+            t = torch.as_tensor(t).to(device=device, dtype=torch.float32).reshape(-1)
+            if t.numel() != n:
+                raise RuntimeError('render_deferred: a parameter of %s has %d elements, expected %d'
+                                   % (type(light).__name__, t.numel(), n))
+            pieces.append(t)
+    if not pieces:
+        return torch.zeros(0, _LIGHT_PARAMS, dtype=torch.float32, device=device), types
+    return torch.cat(pieces).reshape(len(types), _LIGHT_PARAMS), types
+
+
+def _aligned(t, alpha):
+    """contiguous fp32; with alpha the kernels use 8- / 16-byte accesses (a fresh tensor is aligned, an offset view may not be)"""
+    t = t.contiguous()
+    if alpha and t.data_ptr() % 16 != 0:
+        t = t.clone()
+    return t
+
+
+class DeferredShade(torch.autograd.Function):
+    """apply(g_buffer [N, H * aa, W * aa, 9 + alpha], light_params [L, 10], light_types, image_light_ranges, aa_samples, alpha,
+    backend) -> [N, H, W, 3 + alpha].  One native launch forward, one (+ the fold of the light gradients) backward."""
+
+    @staticmethod
+    def forward(ctx, g_buffer, light_params, light_types, image_light_ranges, aa_samples, alpha, backend=None):
+        rd = backend or _default_backend
+        light_types = tuple(int(t) for t in light_types)
+        image_light_ranges = tuple((int(b), int(e)) for b, e in image_light_ranges)
+        aa_samples, alpha = int(aa_samples), bool(alpha)
+        channels = 9 + int(alpha)
+        if g_buffer.dim() != 4 or g_buffer.shape[3] != channels:
+            raise RuntimeError('DeferredShade: the G-buffer must be [N, H * aa, W * aa, %d], got %s'
+                               % (channels, tuple(g_buffer.shape)))
+        n, hg, wg = int(g_buffer.shape[0]), int(g_buffer.shape[1]), int(g_buffer.shape[2])
+        if aa_samples < 1 or hg % aa_samples != 0 or wg % aa_samples != 0 or n == 0 or hg == 0 or wg == 0:
+            raise RuntimeError('DeferredShade: a G-buffer of %d x %d x %d does not divide into aa_samples = %d blocks'
+                               % (n, hg, wg, aa_samples))
+        if tuple(light_params.shape) != (len(light_types), _LIGHT_PARAMS):
+            raise RuntimeError('DeferredShade: light_params must be [%d, %d], got %s'
+                               % (len(light_types), _LIGHT_PARAMS, tuple(light_params.shape)))
+        if len(image_light_ranges) != n:
+            raise RuntimeError('DeferredShade: %d light ranges for %d images' % (len(image_light_ranges), n))
+        if g_buffer.dtype != torch.float32 or light_params.dtype != torch.float32:
+            raise RuntimeError('DeferredShade: fp32 tensors only')
+        device = g_buffer.device
+        use_gpu = device.type == 'cuda'
+        index = device.index if device.index is not None else (torch.cuda.current_device() if use_gpu else 0)
+        g = _aligned(g_buffer.detach(), alpha)
+        params = light_params.detach().to(device).contiguous()
+        h, w = hg // aa_samples, wg // aa_samples
+        image = torch.empty(n, h, w, 3 + int(alpha), dtype=torch.float32, device=device)
+        geometry = (n, h, w, aa_samples, alpha, light_types, image_light_ranges, use_gpu, index)
+        rd.deferred_shade(rd.float_ptr(g.data_ptr()), rd.float_ptr(params.data_ptr()), rd.float_ptr(image.data_ptr()), *geometry)
+        ctx.rd, ctx.geometry, ctx.params_device = rd, geometry, light_params.device
+        ctx.save_for_backward(g, params)
+        return image
+
+    @staticmethod
+    def backward(ctx, grad_img):
+        rd, geometry = ctx.rd, ctx.geometry
+        g, params = ctx.saved_tensors
+        alpha = geometry[4]
+        grad_img = _aligned(grad_img.to(g.device, torch.float32), alpha)
+        assert torch.isfinite(grad_img).all()
+        d_g = torch.empty_like(g)
+        d_params = torch.empty_like(params)
+        rd.deferred_shade_backward(rd.float_ptr(g.data_ptr()), rd.float_ptr(params.data_ptr()), rd.float_ptr(grad_img.data_ptr()),
+                                   rd.float_ptr(d_g.data_ptr()), rd.float_ptr(d_params.data_ptr()), *geometry)
+        return d_g, d_params.to(ctx.params_device), None, None, None, None, None
+
+
+def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None):
+    """Shade a stack of G-buffers [N, H * aa, W * aa, 9 + alpha] in one launch.  `lights`: one list of DeferredLight shared by
+    the N images, or N lists."""
+    n = int(g_buffer.shape[0])
+    per_image = len(lights) > 0 and isinstance(lights[0], (list, tuple))
+    if per_image:
+        if len(lights) != n:
+            raise RuntimeError('render_deferred: %d light lists for %d scenes' % (len(lights), n))
+        flat, ranges = [], []
+        for lgts in lights:
+            ranges.append((len(flat), len(flat) + len(lgts)))
+            flat.extend(lgts)
+    else:
+        flat, ranges = list(lights), [(0, len(lights))] * n
+    params, types = pack_lights(flat, g_buffer.device)
+    return DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend)
+
+
+def _default_device(device):
+    if device is not None:
+        return device
+    return torch.device('cuda:%d' % torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+
+
+def _random_seed():
+    return random.randint(0, 16777216)
+
+
+def _seeds_for(scenes, seed):
+    if seed is None:
+        return [_random_seed() for _ in scenes]
+    if len(seed) != len(scenes):
+        raise RuntimeError('a batch of %d scenes needs a list of %d seeds' % (len(scenes), len(seed)))
+    return list(seed)
+
+
+def _render_g_buffer_for_deferred(scene, seed, channels, aa_samples, sample_pixel_center, use_primary_edge_sampling, device,
+                                  backend):
+    """The scene at aa_samples times its resolution and viewport; both are restored whatever happens."""
+    camera = scene.camera
+    resolution, viewport = camera.resolution, camera.viewport
+    try:
+        camera.resolution = (resolution[0] * aa_samples, resolution[1] * aa_samples)
+        if viewport is not None:
+            camera.viewport = [v * aa_samples for v in viewport]
+        args = RenderFunction.serialize_scene(scene, (1, 1), 0, channels=channels, sampler_type=backend.SamplerType.sobol,
+                                              use_primary_edge_sampling=use_primary_edge_sampling,
+                                              use_secondary_edge_sampling=False, sample_pixel_center=sample_pixel_center,
+                                              device=device, backend=backend)
+    finally:
+        camera.resolution, camera.viewport = resolution, viewport
+    return RenderFunction.apply(seed, *args)
+
+
+def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = False, aa_samples: int = 2, seed=None,
+                    sample_pixel_center: bool = False, use_primary_edge_sampling: bool = True,
+                    device: Optional[torch.device] = None, backend=None):
+    """Deferred rendering: Lambertian shading of the G-buffer by `lights`, no shadows.
+
+    scene: a Scene -> [H, W, 3 | 4]; a list of N scenes of one resolution -> [N, H, W, 3 | 4], shaded in one launch.
+    lights: a list of DeferredLight (shared by all scenes of a batch) or, for a batch, one list per scene.
+    seed: an int (a list of N ints for a batch); random when None.
+    `backend` (redner_amd extension): the module providing the `redner` API, as for RenderFunction.serialize_scene."""
+    backend = backend or _default_backend
+    device = _default_device(device)
+    aa_samples = int(aa_samples)
+    if aa_samples < 1:
+        raise RuntimeError('render_deferred: aa_samples must be at least 1')
+    channels = [backend.channels.position, backend.channels.shading_normal, backend.channels.diffuse_reflectance]
+    if alpha:
+        channels.append(backend.channels.alpha)
+    single = isinstance(scene, Scene) or not isinstance(scene, (list, tuple))
+    scenes = [scene] if single else list(scene)
+    seeds = [_random_seed() if seed is None else seed] if single else _seeds_for(scenes, seed)
+    g_buffers = [_render_g_buffer_for_deferred(sc, se, channels, aa_samples, sample_pixel_center, use_primary_edge_sampling,
+                                               device, backend) for sc, se in zip(scenes, seeds)]
+    g_buffer = g_buffers[0].unsqueeze(0) if single else torch.stack(g_buffers)
+    images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend)
+    return images[0] if single else images
+
+
+def render_generic(scene, channels: List, max_bounces: int = 1, sampler_type=None, num_samples=(4, 4), seed=None,
+                   sample_pixel_center: bool = False, use_primary_edge_sampling: bool = True,
+                   use_secondary_edge_sampling: bool = True, device: Optional[torch.device] = None, backend=None):
+    """Path tracing, G-buffer channels or both: serialize_scene + RenderFunction.apply; a list of scenes is stacked."""
+    backend = backend or _default_backend
+    device = _default_device(device)
+    if sampler_type is None:
+        sampler_type = backend.SamplerType.sobol
+
+    def one(sc, se):
+        args = RenderFunction.serialize_scene(sc, num_samples, max_bounces, channels=channels, sampler_type=sampler_type,
+                                              use_primary_edge_sampling=use_primary_edge_sampling,
+                                              use_secondary_edge_sampling=use_secondary_edge_sampling,
+                                              sample_pixel_center=sample_pixel_center, device=device, backend=backend)
+        return RenderFunction.apply(se, *args)
+
+    if isinstance(scene, Scene) or not isinstance(scene, (list, tuple)):
+        return one(scene, _random_seed() if seed is None else seed)
+    scenes = list(scene)
+    return torch.stack([one(sc, se) for sc, se in zip(scenes, _seeds_for(scenes, seed))])
+
+
+def render_g_buffer(scene, channels: List, num_samples=(1, 1), seed=None, sample_pixel_center: bool = False,
+                    use_primary_edge_sampling: bool = True, use_secondary_edge_sampling: bool = True,
+                    device: Optional[torch.device] = None, backend=None):
+    """The given channels without light transport: max_bounces 0, Sobol sampler."""
+    backend = backend or _default_backend
+    return render_generic(scene, channels, max_bounces=0, sampler_type=backend.SamplerType.sobol, num_samples=num_samples,
+                          seed=seed, sample_pixel_center=sample_pixel_center,
+                          use_primary_edge_sampling=use_primary_edge_sampling,
+                          use_secondary_edge_sampling=use_secondary_edge_sampling, device=device, backend=backend)
+
+
+def render_pathtracing(scene, alpha: bool = False, max_bounces: int = 1, sampler_type=None, num_samples=(4, 4), seed=None,
+                       sample_pixel_center: bool = False, use_primary_edge_sampling: bool = True,
+                       use_secondary_edge_sampling: bool = True, device: Optional[torch.device] = None, backend=None):
+    """Radiance (and alpha) by path tracing; max_bounces 1 = direct lighting only."""
+    backend = backend or _default_backend
+    channels = [backend.channels.radiance] + ([backend.channels.alpha] if alpha else [])
+    return render_generic(scene, channels, max_bounces=max_bounces, sampler_type=sampler_type, num_samples=num_samples,
+                          seed=seed, sample_pixel_center=sample_pixel_center,
+                          use_primary_edge_sampling=use_primary_edge_sampling,
+                          use_secondary_edge_sampling=use_secondary_edge_sampling, device=device, backend=backend)
+
+
+def render_albedo(scene, alpha: bool = False, num_samples=(16, 4), seed=None, sample_pixel_center: bool = False,
+                  use_primary_edge_sampling: bool = True, device: Optional[torch.device] = None, backend=None):
+    """The diffuse reflectance (and alpha) of the first hit."""
+    backend = backend or _default_backend
+    channels = [backend.channels.diffuse_reflectance] + ([backend.channels.alpha] if alpha else [])
+    return render_g_buffer(scene, channels, num_samples=num_samples, seed=seed, sample_pixel_center=sample_pixel_center,
+                           use_primary_edge_sampling=use_primary_edge_sampling, device=device, backend=backend)
