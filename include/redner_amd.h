@@ -273,6 +273,32 @@ int rdr_deferred_shade(const rdr_deferred_desc *desc, const float *g_buffer, con
 int rdr_deferred_shade_backward(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params,
                                 const float *d_image, float *d_g_buffer, float *d_light_params);
 
+/* The mip pyramid of an image texture (pyredner/texture.py:34-69, Texture.generate_mipmap) and its adjoint (csrc/mipmap.h).
+ * texels are [height, width, channels] fp32, all three >= 1.  num_levels = min(ceil(log2(max(height, width))) + 1, 8)
+ * (rdr_mip_num_levels); level l + 1 is max(Hl / 2, 1) x max(Wl / 2, 1), so a side that is not a power of two reaches 1 early and
+ * the last levels repeat at 1 x 1.  A level is the 2 x 2 box filter of the level before it with WRAPPING indices, followed by
+ * the mean over rows [floor(i Hp / Ho), ceil((i + 1) Hp / Ho)) and the like columns (interpolate(mode='area')): the wrapping
+ * [1 2 1] x [1 2 1] / 16 filter at stride 2 for even sides, overlapping windows of 3 for odd sides, the identity for a side of 1.
+ *   rdr_mip_pyramid           levels[0] is the caller's image (read); levels[1 .. num_levels) are written, every element.
+ *   rdr_mip_pyramid_backward  d_texels = g_0 + A_1^T (g_1 + A_2^T (g_2 + ...)), g_l = d_levels[l], A_l = the map from level
+ *                             l - 1 to level l.  d_levels[l] may be NULL (= zeros) and is not modified; every element of d_texels
+ *                             [height, width, channels] is written.  `scratch` holds the partial sums of the levels between:
+ *                             at least rdr_mip_backward_scratch(height, width, channels) floats in the same memory as the
+ *                             tensors (may be NULL when that is 0); its contents afterwards are unspecified.
+ * Both calls fail (rdr_last_error) if num_levels is not what the rule gives, if a size is not positive, a side exceeds 32768 or
+ * the image 2^30 floats, or a required pointer is NULL.  Pointers are DEVICE memory of gpu_index; a negative gpu_index means
+ * host memory and is accepted by the CPU debugging harness only.  fp32 arithmetic in a fixed order, gathers only, no atomics:
+ * results are bitwise reproducible from run to run, and the harness computes the same bits as the kernels.  The library allocates
+ * nothing.  One to three launches per call (one workgroup does a whole pyramid of up to 64 x 64 x 3 floats; otherwise a tiled
+ * launch does three levels at a time while a level is larger than that, and one workgroup the rest: two launches up to
+ * 512 x 512 x 3, three above; the same count backward), ordered on the rdr_set_stream stream and NOT synchronised: the results
+ * are ready for later work on that stream.  Return 0 on success. */
+int rdr_mip_num_levels(int height, int width);                                /* 0 for a size that is not positive */
+int64_t rdr_mip_backward_scratch(int height, int width, int channels);        /* floats; -1 on error */
+int rdr_mip_pyramid(int height, int width, int channels, int num_levels, float *const *levels, int gpu_index);
+int rdr_mip_pyramid_backward(int height, int width, int channels, int num_levels, const float *const *d_levels, float *d_texels,
+                             float *scratch, int64_t scratch_floats, int gpu_index);
+
 /* Message of the last failure on the calling thread ("" if none). */
 const char *rdr_last_error(void);
 

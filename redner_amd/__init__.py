@@ -5,6 +5,8 @@
     redner_amd.render_utils      render_deferred + the deferred lights, render_g_buffer / render_albedo /
                                  render_pathtracing / render_generic; all exported here:
                                  `from redner_amd import render_deferred, PointLight`
+    redner_amd.texture           mip-mapped Texture / EnvironmentMap and generate_mipmap on the native pyramid kernels:
+                                 `from redner_amd import Texture, EnvironmentMap, generate_mipmap`
     redner_amd.install()         register redner_amd.redner as `redner` for the reference's
                                  unmodified pyredner package
 """
@@ -12,6 +14,7 @@ import sys
 
 _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'DeferredShade',
                  'deferred_shade', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo', 'render_pathtracing')
+_TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid')
 
 
 def __getattr__(name):
@@ -19,6 +22,9 @@ def __getattr__(name):
     if name in _RENDER_UTILS:
         from . import render_utils
         return getattr(render_utils, name)
+    if name in _TEXTURE:
+        from . import texture
+        return getattr(texture, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 

@@ -148,7 +148,8 @@ EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_textu
            'rdr_trace_stats_enable', 'rdr_trace_stats_reset', 'rdr_trace_stats_get', 'rdr_scene_trace',
            'rdr_debug_counters_get', 'rdr_trim_cache', 'rdr_debug_dump_edges', 'rdr_debug_bvh_check',
            'rdr_set_stream', 'rdr_set_pool_cap_mb', 'rdr_get_pool_cap_mb', 'rdr_set_build_flags', 'rdr_debug_libm', 'rdr_libm_exact',
-           'rdr_deferred_shade', 'rdr_deferred_shade_backward')
+           'rdr_deferred_shade', 'rdr_deferred_shade_backward',
+           'rdr_mip_num_levels', 'rdr_mip_backward_scratch', 'rdr_mip_pyramid', 'rdr_mip_pyramid_backward')
 
 _lib = None
 _lib_path = None
@@ -213,6 +214,15 @@ def load(path=None):
     lib.rdr_deferred_shade.argtypes = [C.POINTER(DeferredDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rdr_deferred_shade_backward.restype = C.c_int
     lib.rdr_deferred_shade_backward.argtypes = [C.POINTER(DeferredDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rdr_mip_num_levels.restype = C.c_int
+    lib.rdr_mip_num_levels.argtypes = [C.c_int, C.c_int]
+    lib.rdr_mip_backward_scratch.restype = C.c_int64
+    lib.rdr_mip_backward_scratch.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.rdr_mip_pyramid.restype = C.c_int
+    lib.rdr_mip_pyramid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int]
+    lib.rdr_mip_pyramid_backward.restype = C.c_int
+    lib.rdr_mip_pyramid_backward.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_int]
     _lib, _lib_path = lib, path
     return lib
 

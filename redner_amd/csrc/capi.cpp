@@ -4,6 +4,7 @@
 #include "tuning.h"
 #include "edges.h"
 #include "deferred.h"
+#include "mipmap.h"
 #include <cstdio>
 #include "scene.h"
 #include <cstring>
@@ -125,6 +126,56 @@ int rdr_deferred_shade_backward(const rdr_deferred_desc *desc, const float *g_bu
         exec::select_device(desc->gpu_index >= 0, desc->gpu_index);
         use_caller_stream();
         rdr::dfr::shade_backward(*desc, g_buffer, light_params, d_image, d_g_buffer, d_light_params);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_mip_num_levels(int height, int width) { return height > 0 && width > 0 ? rdr::mip::num_levels(height, width) : 0; }
+
+int64_t rdr_mip_backward_scratch(int height, int width, int channels) {
+    try {
+        g_last_error.clear();
+        return (int64_t)rdr::mip::scratch_floats(rdr::mip::make_shape(height, width, channels, rdr_mip_num_levels(height, width),
+                                                                      "rdr_mip_backward_scratch"));
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return -1;
+    }
+}
+
+// the product library reads and writes device memory only; host pointers are for the CPU debugging harness
+static void mip_select(int gpu_index, const char *who) {
+#if !defined(RDR_HOSTSIM)
+    if (gpu_index < 0) throw std::runtime_error(std::string(who) + ": host memory (negative gpu_index) is for the CPU harness only");
+#endif
+    exec::select_device(gpu_index >= 0, gpu_index);
+    use_caller_stream();
+}
+
+int rdr_mip_pyramid(int height, int width, int channels, int num_levels, float *const *levels, int gpu_index) {
+    try {
+        g_last_error.clear();
+        std::lock_guard<std::recursive_mutex> lk(device_lock(gpu_index));
+        mip_select(gpu_index, "rdr_mip_pyramid");
+        rdr::mip::pyramid(height, width, channels, num_levels, levels);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_mip_pyramid_backward(int height, int width, int channels, int num_levels, const float *const *d_levels, float *d_texels,
+                             float *scratch, int64_t scratch_floats, int gpu_index) {
+    try {
+        g_last_error.clear();
+        std::lock_guard<std::recursive_mutex> lk(device_lock(gpu_index));
+        mip_select(gpu_index, "rdr_mip_pyramid_backward");
+        rdr::mip::pyramid_backward(height, width, channels, num_levels, d_levels, d_texels, scratch,
+                                   scratch_floats > 0 ? (size_t)scratch_floats : 0);
         return 0;
     } catch (const std::exception &e) {
         set_error(e.what());

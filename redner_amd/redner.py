@@ -454,6 +454,44 @@ def deferred_shade_backward(g_buffer, light_params, d_image, d_g_buffer, d_light
         raise RuntimeError('redner.deferred_shade_backward: ' + _capi.last_error())
 
 
+def mip_num_levels(height, width):
+    """Not in the reference's module: rdr_mip_num_levels, min(ceil(log2(max(height, width))) + 1, 8)."""
+    return int(_capi.lib().rdr_mip_num_levels(int(height), int(width)))
+
+
+def mip_backward_scratch(height, width, channels):
+    """Not in the reference's module: floats of scratch mip_pyramid_backward needs for an image of this size."""
+    n = int(_capi.lib().rdr_mip_backward_scratch(int(height), int(width), int(channels)))
+    if n < 0:
+        raise RuntimeError('redner.mip_backward_scratch: ' + _capi.last_error())
+    return n
+
+
+def _level_table(levels):
+    return (C.c_void_p * max(len(levels), 1))(*[_addr(l) or None for l in levels])
+
+
+def mip_pyramid(levels, height, width, channels, use_gpu, gpu_index):
+    """Not in the reference's module (its pyramid is torch code, pyredner/texture.py): rdr_mip_pyramid (include/redner_amd.h).
+    levels: float_ptr of every level, [0] the image [height, width, channels]; levels 1.. are written.  Ordered on the
+    current torch stream, not synchronised."""
+    lib = _capi.lib()
+    _use_torch_stream(lib, use_gpu, gpu_index)
+    if lib.rdr_mip_pyramid(int(height), int(width), int(channels), len(levels), _level_table(levels),
+                           int(gpu_index) if use_gpu else -1) != 0:
+        raise RuntimeError('redner.mip_pyramid: ' + _capi.last_error())
+
+
+def mip_pyramid_backward(d_levels, d_texels, scratch, scratch_floats, height, width, channels, use_gpu, gpu_index):
+    """Not in the reference's module: rdr_mip_pyramid_backward.  d_levels: float_ptr per level, float_ptr(0) = zeros; writes every
+    element of d_texels."""
+    lib = _capi.lib()
+    _use_torch_stream(lib, use_gpu, gpu_index)
+    if lib.rdr_mip_pyramid_backward(int(height), int(width), int(channels), len(d_levels), _level_table(d_levels), _addr(d_texels),
+                                    _addr(scratch), int(scratch_floats), int(gpu_index) if use_gpu else -1) != 0:
+        raise RuntimeError('redner.mip_pyramid_backward: ' + _capi.last_error())
+
+
 def _use_torch_stream(lib, use_gpu, gpu_index=None):
     """The library orders its launches on the calling thread's CURRENT torch stream OF THE SCENE'S DEVICE (rdr_set_stream):
     tensors produced under `with torch.cuda.stream(s):` are read after their producers without a device-wide

@@ -10,8 +10,10 @@ The same names and argument meanings are kept so tests read like the reference's
     img.sum().backward()
 
 The scene classes below (Camera, Shape, Material, AreaLight, Scene) carry only what crosses the
-boundary; loaders, mip-map generation, image IO etc. remain the reference's pure-Python package
-(out of scope).  On a machine that has the reference checkout, the
+boundary: `Texture` and `EnvironmentMap` here keep an image as ONE level (or the list of levels
+they are given).  The mip-mapped `redner_amd.Texture` / `redner_amd.EnvironmentMap` of
+redner_amd/texture.py derive from them and build the reference's pyramid with native kernels.
+Loaders, image IO etc. remain the reference's pure-Python package (out of scope).  On a machine that has the reference checkout, the
 unmodified pyredner package can be used instead: `redner_amd.install()`.
 
 `backend` (default: redner_amd.redner) is the module providing the `redner` API; the parity
@@ -108,6 +110,10 @@ class EnvironmentMap:
         self.env_to_world = env_to_world if env_to_world is not None else torch.eye(4, 4)
         self.world_to_env = torch.inverse(self.env_to_world).contiguous()
         self.directly_visible = directly_visible
+        self.generate_envmap_pdf()
+
+    def generate_envmap_pdf(self):
+        """sample_cdf_ys / sample_cdf_xs / pdf_norm from level 0 of `values` (pyredner/envmap.py:36-60)."""
         t = self.values.mipmap[0].detach()
         lum = 0.212671 * t[:, :, 0] + 0.715160 * t[:, :, 1] + 0.072169 * t[:, :, 2]
         cdf_xs_ = torch.cumsum(lum, dim=1)
