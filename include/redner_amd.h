@@ -180,6 +180,9 @@ struct rdr_tuning {
     int refill_order;               /* order in which trace_refill_kernel hands a wave's 256 rays out: 1 = queue order (rounds
                                      * 3-5), 2 = by direction octant (default), 3 = octant x dominant axis               RDR_REFILL_SORT=0|1|2 */
     int pickh_slots_per_lane, pickh_idle_lanes, pickh_steps;     /* the hierarchical pick's descent walk (1, 8, 8)           RDR_PICKH_REFILL=k,idle,steps */
+    int stale_event_cap_plus1;      /* capacity, + 1, of the list of stale hit-position reads that a batched gradient render of an
+                                     * environment-lit scene records (default: one per edge-ray lane); a list that overflows makes
+                                     * the call start over unbatched (tests: 1 = capacity 0)                                 */
 };
 
 /* Library-wide settings (no reference counterpart).

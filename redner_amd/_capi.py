@@ -92,7 +92,8 @@ class Tuning(C.Structure):
                 ('refill_rays_per_lane', C.c_int), ('refill_idle_lanes', C.c_int), ('refill_steps', C.c_int),
                 ('wide_max_rays', C.c_int), ('gather_budget', C.c_int),
                 ('gather_heavy_cap_plus1', C.c_int), ('gather_work_cap_plus1', C.c_int), ('mem_available_mb', C.c_int),
-                ('refill_order', C.c_int), ('pickh_slots_per_lane', C.c_int), ('pickh_idle_lanes', C.c_int), ('pickh_steps', C.c_int)]
+                ('refill_order', C.c_int), ('pickh_slots_per_lane', C.c_int), ('pickh_idle_lanes', C.c_int), ('pickh_steps', C.c_int),
+                ('stale_event_cap_plus1', C.c_int)]
 
 
 # rdr_tune_flags / rdr_build_flags

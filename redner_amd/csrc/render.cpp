@@ -406,6 +406,8 @@ struct Backward {
                 // stale reads across the samples of a batch are recorded and replayed after the sweep (HitPosView)
                 hp_event_cap = L;
                 hp_events = arena.get<HitEvent>((size_t)hp_event_cap);
+                // tests: a short list, so that the restart runs (rdr_tuning::stale_event_cap_plus1)
+                if (tuning().stale_event_cap >= 0) hp_event_cap = std::min(tuning().stale_event_cap, hp_event_cap);
                 hp_event_count = arena.get<int>(1);
                 exec::zero(hp_event_count, sizeof(int));
                 hp_carry = arena.get<double>((size_t)3 * 2 * batch.P0);

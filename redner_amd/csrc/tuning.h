@@ -25,6 +25,7 @@ struct Tuning {
     double mem_available_mb = -1.0;     // < 0: ask the driver
     int refill_sort = 1;                // 0 queue order, 1 octant, 2 octant x axis (trace.hip)
     int pickh_k = 1, pickh_idle = 8, pickh_steps = 8;
+    int stale_event_cap = -1;           // -1 = one entry per edge-ray lane (render.cpp: hp_event_cap)
     bool has(unsigned f) const { return (flags & f) != 0; }
 };
 
@@ -105,6 +106,7 @@ inline Tuning resolve_tuning(const rdr_tuning *t) {
     r.pickh_k = detail::clampi(pick(u.pickh_slots_per_lane, e.pickh_k, 1), 1, 64);
     r.pickh_idle = detail::clampi(pick(u.pickh_idle_lanes, e.pickh_idle, 8), 1, 64);
     r.pickh_steps = detail::clampi(pick(u.pickh_steps, e.pickh_steps, 8), 1, 1024);
+    r.stale_event_cap = u.stale_event_cap_plus1 > 0 ? u.stale_event_cap_plus1 - 1 : -1;
     return r;
 }
 

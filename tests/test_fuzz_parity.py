@@ -702,10 +702,45 @@ def _main(lib):
         d = np.linalg.norm(imgs[1].astype(np.float64) - imgs[0].astype(np.float64))
         if not d <= 1e-4 * n + 1e-9:
             failures['screen gradient %d' % seed] = '%.3e' % (d / max(n, 1e-300))
+    print('ENV ' + json.dumps({k: v for k, v in sorted(os.environ.items()) if k.startswith('RDR_')}))
     print('FLIPS ' + json.dumps(FLIPS))
     print('ORACLE_UNSTABLE ' + json.dumps(ORACLE_UNSTABLE))
     print('SCENES %d' % len(SEEN))
     print('FUZZ ' + json.dumps(failures))
+
+
+def _variant_env(env, keys, variant):
+    """The child's environment for one variant string: every variable of `keys` is taken out first (a leg runs what its string
+    says, whatever the caller's shell has set), then `NAME=value` sets one and `-NAME` REMOVES one that the session itself sets
+    (tests/conftest.py: RDR_LARGE_FRAME_FORMS).  -> (env, {name: value or None}) with what the child must report."""
+    for k in keys:
+        env.pop(k, None)
+    expect = {}
+    for word in variant.split():
+        if word.startswith('-'):
+            env.pop(word[1:], None)
+            expect[word[1:]] = None
+        else:
+            k, v = word.split('=')
+            env[k] = v
+            if k.startswith('RDR_'):
+                expect[k] = v
+    return env, expect
+
+
+def _check_child_env(out, expect):
+    """The child proves what it ran: `_main` prints the RDR_* variables it saw."""
+    seen = json.loads([l for l in out.splitlines() if l.startswith('ENV ')][-1][4:])
+    for k, v in expect.items():
+        if v is None:
+            assert k not in seen, (k, seen)
+        else:
+            assert seen.get(k) == v, (k, seen)
+    return seen
+
+
+HOSTSIM_KEYS = ('RDR_BATCH', 'RDR_FORCE_GENERAL', 'FUZZ_STRIDE', 'RDR_BATCH_LANES', 'RDR_GATHER_BUDGET', 'RDR_GATHER_CAPS', 'RDR_NO_REFIT',
+                'RDR_NO_EDGE_CACHE', 'RDR_NO_FUSED_BOUNCE', 'RDR_PICKH_LEAVES_WALK', 'RDR_PICKH_ONE_LAUNCH', 'RDR_NO_NEE_COMPACT')
 
 
 # the default schedule (sample batches, specialised stage kernels), one sample per launch, no stage specialisation, ragged
@@ -714,17 +749,25 @@ def _main(lib):
                                      'RDR_BATCH_LANES=1000 FUZZ_STRIDE=3',
                                      # the gather's hand-over paths (tiny budgets / list capacities); caches and refits off
                                      'RDR_GATHER_BUDGET=2 RDR_GATHER_CAPS=3,5 FUZZ_STRIDE=4', 'RDR_GATHER_BUDGET=1 RDR_GATHER_CAPS=0,0 FUZZ_STRIDE=4',
-                                     'RDR_NO_REFIT=1 RDR_NO_EDGE_CACHE=1 FUZZ_STRIDE=4'])
+                                     'RDR_NO_REFIT=1 RDR_NO_EDGE_CACHE=1 FUZZ_STRIDE=4',
+                                     # what the library picks BY ITSELF for frames below 2^19 lanes -- every optimisation loop --
+                                     # (one-launch hierarchical pick, adjoint lists as they are): the session's variable taken out
+                                     '-RDR_LARGE_FRAME_FORMS FUZZ_STRIDE=3',
+                                     # the two-stage lean bounce: what every frame above 2^19 lanes runs and these small ones never do
+                                     'RDR_NO_FUSED_BOUNCE=1 FUZZ_STRIDE=3',
+                                     # the walk form of the split pick's leaves stage (with the session's large-frame forms: it
+                                     # belongs to the split pick)
+                                     'RDR_PICKH_LEAVES_WALK=1 FUZZ_STRIDE=4'])
 def test_random_scenes_hostsim_vs_oracle(hostsim_backend, variant):
     from conftest import HOSTSIM_LIB
     here = os.path.dirname(os.path.abspath(__file__))
     env = dict(os.environ, MALLOC_MMAP_THRESHOLD_='1024', MALLOC_PERTURB_='255',
                PYTHONPATH=os.pathsep.join([os.path.dirname(here), here, os.environ.get('PYTHONPATH', '')]))
-    for k in ('RDR_BATCH', 'RDR_FORCE_GENERAL', 'FUZZ_STRIDE', 'RDR_BATCH_LANES', 'RDR_GATHER_BUDGET', 'RDR_GATHER_CAPS', 'RDR_NO_REFIT',
-              'RDR_NO_EDGE_CACHE'):
-        env.pop(k, None)
-    env.update(dict(kv.split('=') for kv in variant.split()))
+    env, expect = _variant_env(env, HOSTSIM_KEYS, variant)
+    if 'RDR_LARGE_FRAME_FORMS' not in expect:
+        expect['RDR_LARGE_FRAME_FORMS'] = os.environ['RDR_LARGE_FRAME_FORMS']          # (tests/conftest.py)
     out = subprocess.check_output([sys.executable, os.path.abspath(__file__), HOSTSIM_LIB], env=env, timeout=1500).decode()
+    _check_child_env(out, expect)
     line = [l for l in out.splitlines() if l.startswith('FUZZ ')][-1]
     assert json.loads(line[5:]) == {}
 
@@ -733,22 +776,28 @@ def test_random_scenes_hostsim_vs_oracle(hostsim_backend, variant):
 # every family above, under the default schedule (sample batches, specialised kernels, side streams), with ragged batches, and
 # with the refilling traversal kernel forced onto every queue (it normally serves queues of >= 2^22 lanes only: bench.py's).
 GPU_KEYS = ('RDR_BATCH', 'RDR_FORCE_GENERAL', 'FUZZ_STRIDE', 'FUZZ_OFFSET', 'RDR_BATCH_LANES', 'RDR_TRACE_REFILL_ALL', 'RDR_NO_OVERLAP',
-            'RDR_TRACE_REFILL', 'RDR_WORKERS')
+            'RDR_TRACE_REFILL', 'RDR_WORKERS', 'RDR_NO_FUSED_BOUNCE', 'RDR_PICKH_LEAVES_WALK', 'RDR_PICKH_ONE_LAUNCH', 'RDR_NO_NEE_COMPACT')
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('variant', ['FUZZ_STRIDE=8', 'RDR_BATCH=3 FUZZ_STRIDE=8 FUZZ_OFFSET=3',
-                                     'RDR_TRACE_REFILL_ALL=1 FUZZ_STRIDE=8 FUZZ_OFFSET=5'])
+                                     'RDR_TRACE_REFILL_ALL=1 FUZZ_STRIDE=8 FUZZ_OFFSET=5',
+                                     # the small-frame forms the library picks by itself (the session's variable taken out), one
+                                     # worker on one stream, the two-stage lean bounce: each from a first seed no other leg uses
+                                     '-RDR_LARGE_FRAME_FORMS FUZZ_STRIDE=8 FUZZ_OFFSET=1',
+                                     'RDR_WORKERS=1 RDR_NO_OVERLAP=1 FUZZ_STRIDE=8 FUZZ_OFFSET=2',
+                                     'RDR_NO_FUSED_BOUNCE=1 FUZZ_STRIDE=8 FUZZ_OFFSET=6'])
 def test_random_scenes_gpu_vs_oracle(gpu_backend, variant):
     here = os.path.dirname(os.path.abspath(__file__))
     # MALLOC_PERTURB_=255: glibc then fills every chunk it hands out with 0x00 (perturb byte ^ 0xff) -- the scratch the
     # reference reads without having written it is zero whether the chunk is a fresh mapping or recycled heap (see _compare)
     env = dict(os.environ, MALLOC_MMAP_THRESHOLD_='1024', MALLOC_PERTURB_='255',
                PYTHONPATH=os.pathsep.join([os.path.dirname(here), here, os.environ.get('PYTHONPATH', '')]))
-    for k in GPU_KEYS:
-        env.pop(k, None)
-    env.update(dict(kv.split('=') for kv in variant.split()))
+    env, expect = _variant_env(env, GPU_KEYS, variant)
+    if 'RDR_LARGE_FRAME_FORMS' not in expect:
+        expect['RDR_LARGE_FRAME_FORMS'] = os.environ['RDR_LARGE_FRAME_FORMS']          # (tests/conftest.py)
     out = subprocess.check_output([sys.executable, os.path.abspath(__file__), 'gpu'], env=env, timeout=900).decode()
+    _check_child_env(out, expect)
     grab = lambda tag: [l for l in out.splitlines() if l.startswith(tag + ' ')][-1][len(tag) + 1:]
     flips, scenes, unstable = json.loads(grab('FLIPS')), int(grab('SCENES')), json.loads(grab('ORACLE_UNSTABLE'))
     path = os.environ.get('RDR_PARITY_REPORT')

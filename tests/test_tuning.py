@@ -127,7 +127,10 @@ def test_unknown_tuning_field_is_an_error(hostsim_backend):
         RenderFunction.apply(1, *args)
 
 
-@pytest.mark.parametrize('case', [CASE, GLOSSY, 'bunny_box_96x96x8', 'envmap_sphere_48x48x4'])
+@pytest.mark.parametrize('case', [CASE, GLOSSY, 'bunny_box_96x96x8', 'envmap_sphere_48x48x4',
+                                  # a mid scene (mip levels, chain mode), a general one (orthographic camera), a second
+                                  # environment-lit one (with area lights and textures)
+                                  'living_room_standin_40x40x2', 'two_triangles_ortho_64x64x4', 'living_room_standin_envmap_32x32x2'])
 def test_adjoint_lists_skip_only_zero_terms_hostsim(hostsim_backend, case):
     """The continuation half of the bounce adjoint runs over the lanes that have something to take over (render.cpp: adj_scatter:
     the next depth's list minus the lanes whose successor record is known to be all zeros, AdjState::carries), the next-event half
