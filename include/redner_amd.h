@@ -298,6 +298,7 @@ int rdr_deferred_shade_backward(const rdr_deferred_desc *desc, const float *g_bu
  * are ready for later work on that stream.  Return 0 on success. */
 int rdr_mip_num_levels(int height, int width);                                /* 0 for a size that is not positive */
 int64_t rdr_mip_backward_scratch(int height, int width, int channels);        /* floats; -1 on error */
+int rdr_mip_tiled_stages(int height, int width, int channels);                /* tiled launches of a call each way; -1 on error */
 int rdr_mip_pyramid(int height, int width, int channels, int num_levels, float *const *levels, int gpu_index);
 int rdr_mip_pyramid_backward(int height, int width, int channels, int num_levels, const float *const *d_levels, float *d_texels,
                              float *scratch, int64_t scratch_floats, int gpu_index);

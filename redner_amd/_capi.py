@@ -150,7 +150,8 @@ EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_textu
            'rdr_debug_counters_get', 'rdr_trim_cache', 'rdr_debug_dump_edges', 'rdr_debug_bvh_check',
            'rdr_set_stream', 'rdr_set_pool_cap_mb', 'rdr_get_pool_cap_mb', 'rdr_set_build_flags', 'rdr_debug_libm', 'rdr_libm_exact',
            'rdr_deferred_shade', 'rdr_deferred_shade_backward',
-           'rdr_mip_num_levels', 'rdr_mip_backward_scratch', 'rdr_mip_pyramid', 'rdr_mip_pyramid_backward')
+           'rdr_mip_num_levels', 'rdr_mip_backward_scratch', 'rdr_mip_tiled_stages', 'rdr_mip_pyramid',
+           'rdr_mip_pyramid_backward')
 
 _lib = None
 _lib_path = None
@@ -219,6 +220,8 @@ def load(path=None):
     lib.rdr_mip_num_levels.argtypes = [C.c_int, C.c_int]
     lib.rdr_mip_backward_scratch.restype = C.c_int64
     lib.rdr_mip_backward_scratch.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.rdr_mip_tiled_stages.restype = C.c_int
+    lib.rdr_mip_tiled_stages.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.rdr_mip_pyramid.restype = C.c_int
     lib.rdr_mip_pyramid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int]
     lib.rdr_mip_pyramid_backward.restype = C.c_int

@@ -146,6 +146,17 @@ int64_t rdr_mip_backward_scratch(int height, int width, int channels) {
     }
 }
 
+int rdr_mip_tiled_stages(int height, int width, int channels) {
+    try {
+        g_last_error.clear();
+        return rdr::mip::tiled_stages(rdr::mip::make_shape(height, width, channels, rdr_mip_num_levels(height, width),
+                                                           "rdr_mip_tiled_stages"));
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return -1;
+    }
+}
+
 // the product library reads and writes device memory only; host pointers are for the CPU debugging harness
 static void mip_select(int gpu_index, const char *who) {
 #if !defined(RDR_HOSTSIM)

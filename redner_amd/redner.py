@@ -467,6 +467,15 @@ def mip_backward_scratch(height, width, channels):
     return n
 
 
+def mip_tiled_stages(height, width, channels):
+    """Not in the reference's module: how many tiled launches (three levels each) mip_pyramid and mip_pyramid_backward make for an
+    image of this size before one workgroup does the rest (csrc/mipmap.h: tiled_stages); 0 = one workgroup does everything."""
+    n = int(_capi.lib().rdr_mip_tiled_stages(int(height), int(width), int(channels)))
+    if n < 0:
+        raise RuntimeError('redner.mip_tiled_stages: ' + _capi.last_error())
+    return n
+
+
 def _level_table(levels):
     return (C.c_void_p * max(len(levels), 1))(*[_addr(l) or None for l in levels])
 

@@ -4,7 +4,10 @@ reference's own deferred-shading code under torch autograd (tests/golden/make_de
 Bars: parity_util.TOL = 1e-4 relative L2 on every whole tensor (image, G-buffer gradient, each light tensor's gradient, and for
 the end-to-end cases the vertex, texel and camera gradients); the expected error is fp32 rounding, 1e-7 ... 1e-6
 (profiles/deferred_shade.txt has the measured maxima).  The harness cases run the same per-texel bodies as the kernels, as
-plain loops; the GPU cases run on both builds of the library."""
+plain loops; the GPU cases run on both builds of the library.
+
+The second half of the file (test_definition_* and after) compares the kernels with an fp64 definition of the four formulas written
+here, per image slice and per light row, where the adjoint's launch plan changes and where the fixtures do not reach."""
 import os
 
 import numpy as np
@@ -282,3 +285,290 @@ def test_render_family_matches_render_function_gpu(gpu_backend):
                        explicit([rd.channels.radiance], (4, 4), 2, rd.SamplerType.sobol, 5))
     both = ru.render_generic([sc, sc], [rd.channels.radiance], seed=[6, 7], device=dev, backend=rd)
     assert torch.equal(both[1], explicit([rd.channels.radiance], (4, 4), 1, rd.SamplerType.sobol, 7))
+
+
+# ---- an independent fp64 definition of shade and adjoint, on both sides of the adjoint's capped grid -------------------------------
+# The fixtures above are 20 x 24 frames with ascending, disjoint light ranges.  The cases below compare the kernels with a
+# definition written here from the four formulas of include/redner_amd.h (torch double, autograd for the adjoint) where the launch
+# plan changes: the capped, striding adjoint grid (deferred.h: kAdjointBlocks), the slab rows of the fold under overlapping /
+# descending / empty light ranges, frames smaller than a wave, aa_samples above 3, spot exponents below 1, and a G-buffer that is
+# only 8-byte aligned.  Bar: parity_util.TOL (1e-4 relative L2) per IMAGE SLICE of the image and of the G-buffer gradient and per
+# LIGHT ROW of the parameter gradient (one wrong image of 64, or one wrong light, cannot hide in the norm of the whole tensor);
+# where the definition is exactly zero (an unlit image, a light no image uses, an entry a light type does not use) the kernels'
+# value must be exactly zero.  The CPU harness has no grid: its legs prove the definition and the bar on the per-texel bodies.
+ADJOINT_BLOCKS = 2048                                  # deferred.h: kAdjointBlocks, the documented cap of the adjoint grid
+USED_COLUMNS = {0: (0, 1, 2), 1: (0, 1, 2, 3, 4, 5), 2: (0, 1, 2, 6, 7, 8), 3: tuple(range(10))}
+SPOT_PLANE_X = 0.25
+_definition_cache = {}
+
+
+def _definition_shade(g, types, params, ranges, aa, alpha):
+    """g [N, H * aa, W * aa, 9 + alpha] and params [L, 10] in torch double -> [N, H, W, 3 + alpha].  One pass per light over the
+    images whose range holds it.  torch.max(x, zeros) splits the gradient at a tie, as the header says.  A spot exponent below 1:
+    pow(c, e) has no finite slope at c == 0, and the documented meaning (deferred.h) is the value pow(0, e)
+    with gradient 0 there -- stated here with `where`, so that no inf * 0 arises."""
+    n, hg, wg, _ = g.shape
+    pos, nrm, alb = g[..., 0:3], g[..., 3:6], g[..., 6:9]
+    rgb = torch.zeros(n, hg, wg, 3, dtype=torch.float64)
+    for l, t in enumerate(types):
+        sel = torch.tensor([k for k, (b, e) in enumerate(ranges) if b <= l < e], dtype=torch.long)
+        if sel.numel() == 0:
+            continue
+        p, nn, a = pos[sel], nrm[sel], alb[sel]
+        intensity = params[l, 0:3]
+        if t == 0:
+            rgb = rgb.index_add(0, sel, intensity * a)
+            continue
+        if t == 2:
+            lv = (-params[l, 6:9] / params[l, 6:9].norm()).expand_as(nn)
+        else:
+            d = params[l, 3:6] - p
+            lv = d / d.norm(dim=-1, keepdim=True)
+        cos = (lv * nn).sum(-1, keepdim=True)
+        c = intensity * torch.max(cos, torch.zeros_like(cos)) * (a / np.pi)
+        if t == 1:
+            c = c / (d * d).sum(-1, keepdim=True)
+        if t == 3:
+            s = -params[l, 6:9] / params[l, 6:9].norm()
+            sc = (lv * s).sum(-1, keepdim=True)
+            sc = torch.max(sc, torch.zeros_like(sc))
+            e = params[l, 9]
+            if float(e.detach()) < 1.0:
+                lit = sc > 0
+                f = torch.where(lit, torch.pow(torch.where(lit, sc, torch.ones_like(sc)), e),
+                                torch.pow(torch.zeros_like(sc), float(e.detach())))
+            else:
+                f = torch.pow(sc, e)
+            c = c * f
+        rgb = rgb.index_add(0, sel, c)
+    img = torch.cat([rgb, g[..., 9:10]], dim=-1) if alpha else rgb
+    return img.reshape(n, hg // aa, aa, wg // aa, aa, img.shape[-1]).mean(dim=(2, 4))
+
+
+def _off_the_kinks(g, types, params, margin=1e-5):
+    """The gradient of max(x, 0) jumps at x == 0: a texel whose fp32 x is +1e-8 where the exact one is -1e-8 differs by its whole
+    gradient, which says nothing about the kernel.  Texels closer than `margin` to a kink of any light WITHOUT being on it get
+    albedo 0 (they then carry no gradient through the clamp); the exact ties (x == 0) stay.  -> (g, how many)"""
+    gd = g.double()
+    pos, nrm = gd[..., 0:3], gd[..., 3:6]
+    near = torch.zeros(g.shape[:3], dtype=torch.bool)
+    for t, row in zip(types, torch.from_numpy(np.asarray(params)).double()):
+        if t == 0:
+            continue
+        if t == 2:
+            lv = (-row[6:9] / row[6:9].norm()).expand_as(nrm)
+        else:
+            lv = (row[3:6] - pos) / (row[3:6] - pos).norm(dim=-1, keepdim=True)
+        xs = [(lv * nrm).sum(-1)]
+        if t == 3:
+            xs.append((lv * (-row[6:9] / row[6:9].norm())).sum(-1))
+        for x in xs:
+            near |= (x != 0) & (x.abs() < margin)
+    g = g.clone()
+    g[..., 6:9] = torch.where(near[..., None], torch.zeros(()), g[..., 6:9])
+    return g, int(near.sum())
+
+
+def _scaled_lights(spec):
+    """the light table of `spec`, every light scaled by its own factor (as test_long_light_list_gpu does): no two rows alike"""
+    types, params = mk.light_table(spec)
+    params = params * (1.0 + 0.001 * np.arange(len(types), dtype=np.float32))[:, None]
+    return [int(t) for t in types], params.astype(np.float32)
+
+
+def _cycled_ranges(n, num_lights):
+    """ranges that differ from image to image: all lights, without the first, without the last, the second half"""
+    kinds = [(0, num_lights), (1, num_lights), (0, num_lights - 1), (num_lights // 2, num_lights)]
+    return tuple(kinds[k % 4] for k in range(n))
+
+
+def _spot_case_inputs(seed, exponents):
+    """Spot lights at x = SPOT_PLANE_X looking along +x (s = (-1, 0, 0) exactly): texels with p_x == SPOT_PLANE_X sit exactly on
+    l.s == 0 (four columns of them, background included), those with smaller p_x are behind the spot.  Every other texel is at
+    least 0.1 away from the plane in x: for e < 1 the slope of pow(c, e) grows without bound as c -> 0+, and no fp32 evaluation of c
+    holds 1e-4 there."""
+    g = mk.synthetic_g_buffer(seed, 1, mk.KERNEL_H, mk.KERNEL_W, 2, 0)
+    dx = g[..., 0] - SPOT_PLANE_X
+    g[..., 0] = torch.where(dx.abs() < 0.1, SPOT_PLANE_X + torch.where(dx < 0, dx - 0.1, dx + 0.1), g[..., 0])
+    wg = g.shape[2]
+    g[:, :, wg // 4: wg // 4 + 4, 0] = SPOT_PLANE_X
+    spec = [(3, {'position': [SPOT_PLANE_X, 0.5 - 0.3 * k, -1.0], 'spot_direction': [2.0, 0.0, 0.0], 'spot_exponent': [e],
+                 'intensity': [4.0 + k, 5.0, 6.0 - k]}) for k, e in enumerate(exponents)]
+    types, params = mk.light_table(spec)
+    assert int((g[..., 0] == SPOT_PLANE_X).sum()) >= 4 * g.shape[1] and int((g[..., 0] < SPOT_PLANE_X).sum()) > 100
+    return g, [int(t) for t in types], params
+
+
+def _build_case(name):
+    """-> dict(g, types, params, ranges, aa, alpha[, capped]); `capped` only for the cases that are about the adjoint grid"""
+    one_each, two_each = mk.light_sets()['one_each'], mk.light_sets()['two_each']
+    kind, _, rest = name.partition('_')
+    seed = 500 + sum(ord(ch) * (k + 1) for k, ch in enumerate(name)) % 1000
+    if kind == 'grid':                                 # grid_<N>x<H>x<W>_<capped|uncapped>
+        shape, _, side = rest.partition('_')
+        n, h, w = (int(v) for v in shape.split('x'))
+        types, params = _scaled_lights(one_each)
+        case = dict(g=mk.synthetic_g_buffer(seed, n, h, w, 1, 1), types=types, params=params, ranges=_cycled_ranges(n, 4), aa=1,
+                    alpha=1, capped=(side == 'capped'))
+    elif kind == 'frame':                              # frame_<H>x<W>_aa<A>: two images, aa 1 without alpha and aa 3 with
+        shape, _, aa = rest.partition('_aa')
+        h, w = (int(v) for v in shape.split('x'))
+        types, params = _scaled_lights(two_each)
+        case = dict(g=mk.synthetic_g_buffer(seed, 2, h, w, int(aa), int(aa) == 3), types=types, params=params,
+                    ranges=((0, 8), (3, 7)), aa=int(aa), alpha=int(int(aa) == 3))
+    elif kind == 'aa':                                 # aa_<A>: 6 x 10 output
+        types, params = _scaled_lights(two_each)
+        case = dict(g=mk.synthetic_g_buffer(seed, 1, 6, 10, int(rest), 1), types=types, params=params, ranges=((0, 8),),
+                    aa=int(rest), alpha=1)
+    elif kind == 'ranges':                             # six lights, four images
+        types, params = _scaled_lights([two_each[k] for k in (0, 2, 4, 6, 3, 7)])
+        ranges = {'overlapping_descending_empty': ((2, 6), (0, 3), (3, 3), (0, 6)),        # the longest range on the LAST image
+                  'longest_first': ((0, 6), (2, 6), (0, 3), (3, 3))}[rest]
+        case = dict(g=mk.synthetic_g_buffer(seed, 4, mk.KERNEL_H, mk.KERNEL_W, 2, 1), types=types, params=params, ranges=ranges,
+                    aa=2, alpha=1)
+    else:
+        assert name == 'spot_exponents'
+        g, types, params = _spot_case_inputs(seed, (0.0, 0.5, 1.0, 3.0))
+        case = dict(g=g, types=types, params=params, ranges=((0, 4),), aa=2, alpha=0)
+    case['g'], case['moved'] = _off_the_kinks(case['g'], case['types'], case['params'])
+    return case
+
+
+def _definition_case(name):
+    """inputs + the fp64 image and gradients, computed once and shared by the harness leg and the GPU legs of both builds"""
+    if name not in _definition_cache:
+        case = _build_case(name)
+        g = case['g'].double().requires_grad_(True)
+        params = torch.from_numpy(case['params']).double().requires_grad_(True)
+        img = _definition_shade(g, case['types'], params, case['ranges'], case['aa'], case['alpha'])
+        up = mk.upstream(img.shape)
+        img.backward(up.double())
+        case.update(up=up, want={'image': img.detach(), 'd_g_buffer': g.grad, 'd_light_params': params.grad})
+        assert all(bool(torch.isfinite(v).all()) for v in case['want'].values()), name
+        _definition_cache[name] = case
+    return _definition_cache[name]
+
+
+def _worst_slice(out, ref, what):
+    """max over the slices [k] of the relative L2 error; a slice whose definition is all zero must be exactly zero"""
+    o, r = out.detach().cpu().double().reshape(out.shape[0], -1), ref.reshape(ref.shape[0], -1)
+    assert o.shape == r.shape and bool(torch.isfinite(o).all()), what
+    rn = r.norm(dim=1)
+    assert bool((o[rn == 0] == 0).all()), what + ': not exactly zero where the definition is'
+    rel = (o - r).norm(dim=1)[rn > 0] / rn[rn > 0]
+    return float(rel.max()) if rel.numel() else 0.0
+
+
+def _run_definition_case(backend, device, name, tag):
+    from redner_amd import render_utils as ru
+    case = _definition_case(name)
+    n, hg, wg, _ = case['g'].shape
+    h, w = hg // case['aa'], wg // case['aa']
+    if 'capped' in case:                               # from the documented cap: is the case on the side it is there for?
+        needed, cap = (h * w + 255) // 256, max(ADJOINT_BLOCKS // n, 1)
+        assert (needed > cap) == case['capped'], (name, needed, cap)
+        assert needed >= cap, (name, needed, cap)      # the uncapped one sits exactly on the cap
+    gl = case['g'].clone().to(device).requires_grad_(True)
+    pl = torch.from_numpy(case['params']).to(device).requires_grad_(True)
+    img = ru.DeferredShade.apply(gl, pl, tuple(case['types']), case['ranges'], case['aa'], bool(case['alpha']), backend)
+    img.backward(case['up'].to(device))
+    out = {'image': img, 'd_g_buffer': gl.grad, 'd_light_params': pl.grad}
+    rep = {k: {'rel_l2': _worst_slice(out[k], case['want'][k], name + ' ' + k), 'tol': parity_util.TOL, 'flipped_rows': 0,
+               'measure': 'the worst light row' if k == 'd_light_params' else 'the worst image slice'} for k in out}
+    print('deferred_definition_' + name, tag, {k: '%.2e' % e['rel_l2'] for k, e in rep.items()}, 'bar %.0e;' % parity_util.TOL,
+          case['moved'], 'texels taken off a kink')
+    parity_util.record('deferred_definition_' + name, rep, tag)
+    d_params = pl.grad.cpu()
+    for l, t in enumerate(case['types']):
+        unused = [k for k in range(10) if k not in USED_COLUMNS[t]]
+        assert bool((d_params[l, unused] == 0).all()), (name, 'light', l, 'an entry its type does not use has a gradient')
+    parity_util.assert_parity(rep, name)
+
+
+GRID_CASES = ['grid_64x96x96_capped', 'grid_2049x20x24_capped', 'grid_1x512x1024_uncapped', 'grid_1x513x1024_capped']
+PLAIN_CASES = ['frame_%dx%d_aa%d' % (h, w, aa) for h, w in ((1, 1), (1, 63), (1, 65), (3, 85), (1, 257)) for aa in (1, 3)] + \
+    ['aa_4', 'aa_5', 'aa_7', 'ranges_overlapping_descending_empty', 'ranges_longest_first', 'spot_exponents']
+
+
+@pytest.mark.parametrize('name', PLAIN_CASES)
+def test_definition_hostsim(hostsim_backend, name):
+    _run_definition_case(hostsim_backend, torch.device('cpu'), name, 'hostsim')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', GRID_CASES + PLAIN_CASES)
+def test_definition_gpu(gpu_backend, name):
+    _run_definition_case(gpu_backend, torch.device('cuda:0'), name, 'gpu')
+
+
+def _run_spot_behind_case(backend, device):
+    """One spot light with exponent 0.5: a texel on l.s == 0 or behind the spot gets NO gradient at all -- pow(0, 0.5) = 0 takes
+    the light away and the documented slope of pow at 0 is 0 where the reference has inf * 0 = NaN -- and the light's parameters
+    get none from it.  Exactly zero, and everything finite."""
+    from redner_amd import render_utils as ru
+    g, types, params = _spot_case_inputs(77, (0.5,))
+    gl = g.clone().to(device).requires_grad_(True)
+    pl = torch.from_numpy(params).to(device).requires_grad_(True)
+    img = ru.DeferredShade.apply(gl, pl, tuple(types), ((0, 1),), 2, False, backend)
+    img.backward(mk.upstream(img.shape).to(device))
+    dark = g[..., 0] <= SPOT_PLANE_X
+    d_g = gl.grad.cpu()
+    assert bool(torch.isfinite(d_g).all()) and bool(torch.isfinite(pl.grad).all()) and bool(torch.isfinite(img).all())
+    assert bool((d_g[dark] == 0).all()) and float(d_g[~dark].abs().sum()) > 0
+    # with every texel on the plane or behind it the light's own gradient is exactly zero too
+    g[..., 0] = torch.where(dark, g[..., 0], torch.full((), SPOT_PLANE_X))
+    gl = g.clone().to(device).requires_grad_(True)
+    pl = torch.from_numpy(params).to(device).requires_grad_(True)
+    img = ru.DeferredShade.apply(gl, pl, tuple(types), ((0, 1),), 2, False, backend)
+    img.backward(mk.upstream(img.shape).to(device))
+    assert bool((img == 0).all()) and bool((gl.grad == 0).all()) and bool((pl.grad == 0).all())
+
+
+def test_spot_exponent_below_one_behind_hostsim(hostsim_backend):
+    _run_spot_behind_case(hostsim_backend, torch.device('cpu'))
+
+
+@pytest.mark.gpu
+def test_spot_exponent_below_one_behind_gpu(gpu_backend):
+    _run_spot_behind_case(gpu_backend, torch.device('cuda:0'))
+
+
+def _run_alignment_case(rd, device):
+    """The C ABI promises 8-byte alignment of an alpha G-buffer (40-byte texels read as 8-byte pairs); the Python surface clones
+    anything that is not 16-byte aligned and never gets there.  Through the raw entry points: the G-buffer and its gradient as
+    views of flat tensors at an offset of 2 floats (8 mod 16), the images 16-byte aligned.  Bit for bit what the aligned call
+    gives, and nothing written outside the view."""
+    n, h, w, aa = 2, mk.KERNEL_H, mk.KERNEL_W, 2
+    g = mk.synthetic_g_buffer(41, n, h, w, aa, 1).to(device)
+    types, params = _scaled_lights(mk.light_sets()['one_each'])
+    params = torch.from_numpy(params).to(device)
+    up = mk.upstream((n, h, w, 4)).to(device)
+    ranges, use_gpu = [(0, 4), (1, 3)], device.type == 'cuda'
+    ptr = lambda t: rd.float_ptr(t.data_ptr())
+
+    def run(offset):
+        flat_g, flat_d = torch.zeros(g.numel() + 4, device=device), torch.full((g.numel() + 4,), 7.0, device=device)
+        gv, dv = (f[offset: offset + g.numel()].view(g.shape) for f in (flat_g, flat_d))
+        gv.copy_(g)
+        assert flat_g.data_ptr() % 16 == 0 and gv.data_ptr() % 16 == dv.data_ptr() % 16 == (4 * offset) % 16
+        img, d_params = torch.empty(n, h, w, 4, device=device), torch.empty_like(params)
+        assert img.data_ptr() % 16 == 0 and up.data_ptr() % 16 == 0
+        rd.deferred_shade(ptr(gv), ptr(params), ptr(img), n, h, w, aa, True, types, ranges, use_gpu, 0)
+        rd.deferred_shade_backward(ptr(gv), ptr(params), ptr(up), ptr(dv), ptr(d_params), n, h, w, aa, True, types, ranges,
+                                   use_gpu, 0)
+        assert bool((flat_d[:offset] == 7.0).all()) and bool((flat_d[offset + g.numel():] == 7.0).all())
+        return img.cpu(), dv.cpu().clone(), d_params.cpu()
+
+    aligned, shifted = run(0), run(2)
+    assert float(aligned[0].abs().sum()) > 0 and float(aligned[2].abs().sum()) > 0
+    for a, b in zip(aligned, shifted):
+        assert torch.equal(a, b)
+
+
+def test_g_buffer_aligned_to_8_bytes_hostsim(hostsim_backend):
+    _run_alignment_case(hostsim_backend, torch.device('cpu'))
+
+
+@pytest.mark.gpu
+def test_g_buffer_aligned_to_8_bytes_gpu(gpu_backend):
+    _run_alignment_case(gpu_backend, torch.device('cuda:0'))

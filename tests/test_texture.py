@@ -10,6 +10,9 @@ Bars
     the 2 x 2 box, up to 8 additions and one division for a 3 x 3 window; the scaling by 1/4 is exact), each at most 2^-24 of a
     value bounded by the input's maximum, averaging never amplifies an error, and at most 7 levels are built.  A wrong weight,
     window or wrap is off by 1e-2 or more.
+  * launch plan (section 3b): the same forward bar, and d_texels element by element against the fp64 adjoint (autograd through
+    a torch-double port of the definition) to 18 * (levels - 1) * 2^-24 * M_0, M_0 being that adjoint of |g| (_run_plan_case has
+    the derivation), at shapes on both sides of every switch of the kernels' launch plan; each case asserts its stage count.
   * adjoint identity: <A x, y> == <x, A^T y> to 1e-5 relative in fp64 accumulation (the two sides differ by the fp32 rounding
     of A x and A^T y, about 1e-7; a wrong transpose is off by percents).
 The harness cases run the same per-texel bodies as the kernels, as plain loops; the GPU cases run on both builds of the library.
@@ -183,6 +186,149 @@ def test_pyramid_definition_hostsim(hostsim_backend, size):
 @pytest.mark.parametrize('size', DEFINITION_SIZES_GPU, ids=mt.size_tag)
 def test_pyramid_definition_gpu(gpu_backend, size):
     _run_definition_case(gpu_backend, GPU, size)
+
+
+# ---- 3b. forward AND adjoint, element by element, on both sides of every switch of the launch plan ------------------------------
+# (H, W, C) -> tiled launches each way.  The rule (csrc/mipmap.h, tiled_stages): a tiled launch does three levels while the level it
+# starts from holds more than 64 * 64 * 3 floats and three more levels exist; one workgroup (the chain kernels) does the rest.
+# The counts are written out, checked against the rule as restated in _stages_by_rule and against what the loaded library
+# plans (rdr_mip_tiled_stages): moving kSmall cannot silently move a case to the other side of its switch.
+PLAN_CASES = [
+    # the kSmall switch: the last chain-only shape and the first tiled ones
+    ((1, 12288, 1), 0), ((1, 12289, 1), 1), ((64, 65, 3), 1), ((65, 64, 3), 1),
+    # sides of 1, 2, 3 inside a tiled launch (h[1..3] or w[1..3] = 1)
+    ((1, 5000, 3), 1), ((13000, 1, 1), 1), ((2, 3000, 4), 1), ((3, 2100, 3), 1), ((5, 1000, 3), 1),
+    # the chunked kernels (C not 1 or 3): one chunk, a full chunk, full + partial chunks
+    ((129, 97, 2), 1), ((128, 32, 4), 1), ((257, 255, 5), 1), ((33, 1241, 6), 1), ((131, 259, 7), 1),
+    # two tiled stages: the second adjoint stage reads `top` from scratch the first wrote
+    ((520, 530, 3), 2), ((1100, 900, 1), 2), ((512, 768, 4), 2), ((521, 770, 5), 2),
+]
+# (size, stages, the only levels that carry an upstream gradient): d_levels[l] = NULL for the others
+MISSING_CASES = [((520, 530, 3), 2, (2,)), ((520, 530, 3), 2, (5,)), ((257, 255, 5), 1, (2,)), ((257, 255, 5), 1, (5,))]
+K_SMALL_FLOATS = 64 * 64 * 3
+# Roundings of one level of the adjoint, counted from up_texel: a fine texel gathers from at most 3 x 3 coarse texels (the
+# windows that hold row r or r - 1: two, three where the range wraps); each term is one division by the window's count (the
+# weight 0.25 * m_r * m_c is a power of two: exact), the terms are added one by one (the first to 0.0: exact): 9 + 8, and one
+# more for the addition of g_l (for level 0 that addition is autograd's).  18, not the 28 a count of every operation gives.
+ADJOINT_ROUNDINGS_PER_LEVEL = 18
+_plan_reference_cache = {}
+
+
+def _stages_by_rule(size):
+    h, w, c = size
+    n = min((max(h, w) - 1).bit_length() + 1, 8)
+    stages = 0
+    while 3 * stages + 3 < n and h * w * c > K_SMALL_FLOATS:
+        stages += 1
+        for _ in range(3):
+            h, w = max(h // 2, 1), max(w // 2, 1)
+    return stages
+
+
+def _definition_level_torch(p):
+    """_definition_level in torch double, so that autograd transposes it: wrap by index, windows by floor / ceil, a SCATTER of
+    every window offset under autograd -- not the kernels' gather with its m_r, m_c multiplicities."""
+    hp, wp = p.shape[0], p.shape[1]
+    ho, wo = max(hp // 2, 1), max(wp // 2, 1)
+    rows, cols = (torch.arange(hp) + 1) % hp, (torch.arange(wp) + 1) % wp
+    b = (p + p[:, cols] + p[rows] + p[rows][:, cols]) / 4.0
+    r0 = (torch.arange(ho) * hp) // ho
+    r1 = -((-(torch.arange(ho) + 1) * hp) // ho)
+    c0 = (torch.arange(wo) * wp) // wo
+    c1 = -((-(torch.arange(wo) + 1) * wp) // wo)
+    out = torch.zeros(ho, wo, p.shape[2], dtype=torch.float64)
+    for dr in range(int((r1 - r0).max())):
+        rsel = (r0 + dr < r1)[:, None, None]
+        for dc in range(int((c1 - c0).max())):
+            csel = (c0 + dc < c1)[None, :, None]
+            out = out + b[torch.clamp(r0 + dr, max=hp - 1)][:, torch.clamp(c0 + dc, max=wp - 1)] * (rsel & csel)
+    return out / ((r1 - r0)[:, None, None] * (c1 - c0)[None, :, None])
+
+
+def _plan_reference(size, present):
+    """Computed once per case and shared by the harness leg and the GPU legs of both builds: the fp32 inputs, the fp64 levels
+    (numpy definition), the fp64 adjoint of the upstream gradients (autograd through the torch definition) and M_0, the same
+    adjoint applied to their absolute values."""
+    key = (size, present)
+    if key not in _plan_reference_cache:
+        gen = torch.Generator().manual_seed(1000 * size[0] + size[1] + size[2])
+        texels = torch.rand(*size, generator=gen) * 2.0 - 0.5
+        want_levels = _definition(texels.numpy())
+        x = texels.double().requires_grad_(True)
+        ref = [x]
+        for _ in range(1, len(want_levels)):
+            ref.append(_definition_level_torch(ref[-1]))
+        for a, b in zip(ref, want_levels):            # the two statements of the definition agree
+            assert tuple(a.shape) == tuple(b.shape) and float(np.abs(a.detach().numpy() - b).max()) <= 1e-14
+        ups = [(torch.rand(*l.shape, generator=gen) - 0.4) if present is None or k in present else None
+               for k, l in enumerate(ref)]
+        used = [k for k, u in enumerate(ups) if u is not None]
+        want_grad, = torch.autograd.grad([ref[k] for k in used], x, [ups[k].double() for k in used], retain_graph=True)
+        m0, = torch.autograd.grad([ref[k] for k in used], x, [ups[k].double().abs() for k in used])
+        _plan_reference_cache[key] = (texels, want_levels, ups, want_grad.numpy(), m0.numpy())
+    return _plan_reference_cache[key]
+
+
+def _run_plan_case(backend, device, size, stages, present, tag):
+    """Forward bar: the one of _run_definition_case.  Adjoint bar, derived the same way: with M_l = |g_l| + A^T M_{l+1} (the
+    fp64 adjoint applied to |g|), every partial sum that up_texel forms for a texel of level l is bounded by M_l, each of its
+    ADJOINT_ROUNDINGS_PER_LEVEL roundings is at most 2^-24 of such a sum, and A^T (non-negative weights) carries an error
+    bounded by e M_{l+1} into one bounded by e A^T M_{l+1} <= e M_l.  So |acc_0 - exact| <= K 2^-24 M_0 element by element with
+    K = 18 x the levels below the top (at most 7) <= 126, to first order (the second-order terms are 1e-6 of that).  A dropped
+    term or a wrong weight is off by 1e-2 M_0 or more in the texels it touches: more than 1000 bars."""
+    assert stages == _stages_by_rule(size) == backend.mip_tiled_stages(*size), (size, stages)
+    texels, want_levels, ups, want_grad, m0 = _plan_reference(size, present)
+    x = texels.clone().to(device).requires_grad_(True)                # (a copy: the shared inputs stay as they are)
+    levels = _texture_module().generate_mipmap(x, backend=backend)
+    assert [tuple(l.shape) for l in levels] == [tuple(l.shape) for l in want_levels]
+    bound = 84.0 * 2.0 ** -24 * float(texels.abs().max())
+    worst = 0.0
+    for l, (got, ref) in enumerate(zip(levels, want_levels)):
+        err = float(np.abs(got.detach().cpu().numpy().astype(np.float64) - ref).max())
+        worst = max(worst, err)
+        assert err <= bound, (size, 'level', l, err, bound)
+    used = [k for k, u in enumerate(ups) if u is not None]
+    torch.autograd.backward([levels[k] for k in used], [ups[k].to(device) for k in used])
+    k_bar = ADJOINT_ROUNDINGS_PER_LEVEL * (len(levels) - 1)
+    err = np.abs(x.grad.cpu().numpy().astype(np.float64) - want_grad)
+    units = float(np.max(np.where(m0 > 0.0, err / np.where(m0 > 0.0, m0, 1.0), np.where(err > 0.0, np.inf, 0.0)))) * 2.0 ** 24
+    name = 'texture_plan_%s%s' % (mt.size_tag(size), '' if present is None else '_only%d' % present[0])
+    print(name, tag, 'stages %d: levels max abs error %.3e (bar %.3e); d_texels max error / M_0 = %.2f x 2^-24 (bar %d x 2^-24)'
+          % (stages, worst, bound, units, k_bar))
+    amax = float(texels.abs().max())
+    parity_util.record(name, {'levels': {'rel_l2': worst / amax, 'tol': bound / amax, 'flipped_rows': 0,
+                                         'measure': 'max |error| over all levels / max |texels|'},
+                              'd_texels': {'rel_l2': units * 2.0 ** -24, 'tol': k_bar * 2.0 ** -24, 'flipped_rows': 0,
+                                           'measure': 'max over the elements of |error| / M_0'}}, tag)
+    assert float(m0.min()) >= 0.0 and units <= k_bar, (size, present, units, k_bar)
+
+
+_plan_ids = [mt.size_tag(s) for s, _ in PLAN_CASES]
+_missing_ids = ['%s_only%d' % (mt.size_tag(s), p[0]) for s, _, p in MISSING_CASES]
+
+
+@pytest.mark.parametrize('size,stages', PLAN_CASES, ids=_plan_ids)
+def test_launch_plan_values_hostsim(hostsim_backend, size, stages):
+    """The per-texel bodies alone (the harness has no launch plan): proves the definitions and the bars before the GPU leg."""
+    _run_plan_case(hostsim_backend, CPU, size, stages, None, 'hostsim')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('size,stages', PLAN_CASES, ids=_plan_ids)
+def test_launch_plan_values_gpu(gpu_backend, size, stages):
+    _run_plan_case(gpu_backend, GPU, size, stages, None, 'gpu')
+
+
+@pytest.mark.parametrize('size,stages,present', MISSING_CASES, ids=_missing_ids)
+def test_launch_plan_missing_level_gradients_hostsim(hostsim_backend, size, stages, present):
+    _run_plan_case(hostsim_backend, CPU, size, stages, present, 'hostsim')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('size,stages,present', MISSING_CASES, ids=_missing_ids)
+def test_launch_plan_missing_level_gradients_gpu(gpu_backend, size, stages, present):
+    """d_levels[l] = NULL inside the tiled adjoint (G reads as zeros) and as the chain's start."""
+    _run_plan_case(gpu_backend, GPU, size, stages, present, 'gpu')
 
 
 # ---- 4. adjoint identity, constants ---------------------------------------------------------------------------------------------
