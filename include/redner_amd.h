@@ -303,6 +303,38 @@ int rdr_mip_pyramid(int height, int width, int channels, int num_levels, float *
 int rdr_mip_pyramid_backward(int height, int width, int channels, int num_levels, const float *const *d_levels, float *d_texels,
                              float *scratch, int64_t scratch_floats, int gpu_index);
 
+/* Smooth vertex normals of a triangle mesh (pyredner/shape.py:7-127, compute_vertex_normal) and their vertex adjoint
+ * (csrc/vertex_normal.h, which pins the meaning, the arithmetic and the summation order).  vertices [V, 3] fp32, indices [T, 3]
+ * int32, normals [V, 3] fp32.
+ *   rdr_mesh_topology_create   the plan of one connectivity: validates (V >= 1, T >= 0, 3 T < 2^31, every index in [0, V); NULL
+ *                              and rdr_last_error otherwise), copies `indices` and builds the rows of corners incident to every
+ *                              vertex, each in ascending corner id 3 f + k.  `indices` is DEVICE memory of gpu_index when use_gpu
+ *                              is set, host memory otherwise (accepted by the CPU debugging harness only).  Synchronises once.
+ *                              Reuse the plan for every call with these indices; destroy it with rdr_mesh_topology_destroy.
+ *   rdr_mesh_topology_read     test hook: row offsets [V + 1] and the corner list [3 T] into HOST memory.
+ *   rdr_vertex_normal_scratch  floats the three buffers of a scheme need: `forward_floats` (scratch of rdr_vertex_normal),
+ *                              `backward_floats` (scratch of rdr_vertex_normal_backward), `saved_floats` (what the forward
+ *                              call saves for the backward call: the unnormalised sums).  Any of the three may be NULL.
+ *   rdr_vertex_normal          writes every element of normals and saved.
+ *   rdr_vertex_normal_backward writes every element of d_vertices [V, 3] from d_normals [V, 3], the vertices and `saved` of the
+ *                              forward call.  The gradient of a degenerate corner or face, and of a vertex whose normal is the
+ *                              (0, 0, 1) default, is 0.
+ * The tensors and scratch are memory of the plan's place; the scratch contents afterwards are unspecified and it may be NULL
+ * when the count is 0.  The library allocates nothing per call.  Two launches each way, ordered on the rdr_set_stream stream
+ * and NOT synchronised.  Gathers and plain stores in a fixed order, no float atomics: bitwise reproducible from run to run,
+ * and the harness computes the same bits as the kernels.  Return 0 on success. */
+typedef enum { rdr_normal_weighting_max = 0, rdr_normal_weighting_cotangent = 1 } rdr_normal_weighting;
+typedef struct rdr_mesh_topology rdr_mesh_topology;
+rdr_mesh_topology *rdr_mesh_topology_create(const int *indices, int num_triangles, int num_vertices, int use_gpu, int gpu_index);
+void rdr_mesh_topology_destroy(rdr_mesh_topology *topology);
+int rdr_mesh_topology_read(const rdr_mesh_topology *topology, int *offsets, int *corners);
+int rdr_vertex_normal_scratch(const rdr_mesh_topology *topology, int scheme, int64_t *forward_floats, int64_t *backward_floats,
+                              int64_t *saved_floats);
+int rdr_vertex_normal(const rdr_mesh_topology *topology, int scheme, const float *vertices, float *normals, float *saved,
+                      float *scratch, int64_t scratch_floats);
+int rdr_vertex_normal_backward(const rdr_mesh_topology *topology, int scheme, const float *vertices, const float *saved,
+                               const float *d_normals, float *d_vertices, float *scratch, int64_t scratch_floats);
+
 /* Message of the last failure on the calling thread ("" if none). */
 const char *rdr_last_error(void);
 

@@ -7,6 +7,8 @@
                                  `from redner_amd import render_deferred, PointLight`
     redner_amd.texture           mip-mapped Texture / EnvironmentMap and generate_mipmap on the native pyramid kernels:
                                  `from redner_amd import Texture, EnvironmentMap, generate_mipmap`
+    redner_amd.shape             compute_vertex_normal on the native vertex-normal kernels (a vertex gradient included):
+                                 `from redner_amd import compute_vertex_normal, MeshTopology`
     redner_amd.install()         register redner_amd.redner as `redner` for the reference's
                                  unmodified pyredner package
 """
@@ -15,6 +17,7 @@ import sys
 _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'DeferredShade',
                  'deferred_shade', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo', 'render_pathtracing')
 _TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid')
+_SHAPE = ('compute_vertex_normal', 'MeshTopology', 'VertexNormals')
 
 
 def __getattr__(name):
@@ -25,6 +28,9 @@ def __getattr__(name):
     if name in _TEXTURE:
         from . import texture
         return getattr(texture, name)
+    if name in _SHAPE:
+        from . import shape
+        return getattr(shape, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 

@@ -151,7 +151,9 @@ EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_textu
            'rdr_set_stream', 'rdr_set_pool_cap_mb', 'rdr_get_pool_cap_mb', 'rdr_set_build_flags', 'rdr_debug_libm', 'rdr_libm_exact',
            'rdr_deferred_shade', 'rdr_deferred_shade_backward',
            'rdr_mip_num_levels', 'rdr_mip_backward_scratch', 'rdr_mip_tiled_stages', 'rdr_mip_pyramid',
-           'rdr_mip_pyramid_backward')
+           'rdr_mip_pyramid_backward',
+           'rdr_mesh_topology_create', 'rdr_mesh_topology_destroy', 'rdr_mesh_topology_read', 'rdr_vertex_normal_scratch',
+           'rdr_vertex_normal', 'rdr_vertex_normal_backward')
 
 _lib = None
 _lib_path = None
@@ -227,6 +229,19 @@ def load(path=None):
     lib.rdr_mip_pyramid_backward.restype = C.c_int
     lib.rdr_mip_pyramid_backward.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                              C.c_int64, C.c_int]
+    lib.rdr_mesh_topology_create.restype = C.c_void_p
+    lib.rdr_mesh_topology_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.rdr_mesh_topology_destroy.restype = None
+    lib.rdr_mesh_topology_destroy.argtypes = [C.c_void_p]
+    lib.rdr_mesh_topology_read.restype = C.c_int
+    lib.rdr_mesh_topology_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rdr_vertex_normal_scratch.restype = C.c_int
+    lib.rdr_vertex_normal_scratch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.rdr_vertex_normal.restype = C.c_int
+    lib.rdr_vertex_normal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.rdr_vertex_normal_backward.restype = C.c_int
+    lib.rdr_vertex_normal_backward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int64]
     _lib, _lib_path = lib, path
     return lib
 

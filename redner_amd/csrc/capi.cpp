@@ -5,6 +5,7 @@
 #include "edges.h"
 #include "deferred.h"
 #include "mipmap.h"
+#include "vertex_normal.h"
 #include <cstdio>
 #include "scene.h"
 #include <cstring>
@@ -187,6 +188,93 @@ int rdr_mip_pyramid_backward(int height, int width, int channels, int num_levels
         mip_select(gpu_index, "rdr_mip_pyramid_backward");
         rdr::mip::pyramid_backward(height, width, channels, num_levels, d_levels, d_texels, scratch,
                                    scratch_floats > 0 ? (size_t)scratch_floats : 0);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+// ---- vertex normals (csrc/vertex_normal.h) ----
+static const rdr::vnrm::Topology &topology_of(const rdr_mesh_topology *topology, const char *who) {
+    if (!topology) throw std::runtime_error(std::string(who) + ": a topology is required");
+    return *reinterpret_cast<const rdr::vnrm::Topology *>(topology);
+}
+
+rdr_mesh_topology *rdr_mesh_topology_create(const int *indices, int num_triangles, int num_vertices, int use_gpu, int gpu_index) {
+    try {
+        g_last_error.clear();
+        const int place = use_gpu ? (gpu_index < 0 ? 0 : gpu_index) : -1;
+        std::lock_guard<std::recursive_mutex> lk(device_lock(place));
+        mip_select(place, "rdr_mesh_topology_create");
+        return reinterpret_cast<rdr_mesh_topology *>(rdr::vnrm::create_topology(indices, num_triangles, num_vertices, place));
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return nullptr;
+    }
+}
+
+void rdr_mesh_topology_destroy(rdr_mesh_topology *topology) {
+    if (!topology) return;
+    rdr::vnrm::Topology *t = reinterpret_cast<rdr::vnrm::Topology *>(topology);
+    std::lock_guard<std::recursive_mutex> lk(device_lock(t->gpu_index));
+    try { exec::select_device(t->gpu_index >= 0, t->gpu_index); } catch (const std::exception &) {}
+    delete t;
+}
+
+int rdr_mesh_topology_read(const rdr_mesh_topology *topology, int *offsets, int *corners) {
+    try {
+        g_last_error.clear();
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_mesh_topology_read");
+        std::lock_guard<std::recursive_mutex> lk(device_lock(t.gpu_index));
+        mip_select(t.gpu_index, "rdr_mesh_topology_read");
+        rdr::vnrm::read_topology(t, offsets, corners);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_vertex_normal_scratch(const rdr_mesh_topology *topology, int scheme, int64_t *forward_floats, int64_t *backward_floats,
+                              int64_t *saved_floats) {
+    try {
+        g_last_error.clear();
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_vertex_normal_scratch");
+        const bool cot = rdr::vnrm::cotangent(scheme, "rdr_vertex_normal_scratch");
+        if (forward_floats) *forward_floats = (int64_t)rdr::vnrm::forward_scratch_floats(t, cot);
+        if (backward_floats) *backward_floats = (int64_t)rdr::vnrm::backward_scratch_floats(t, cot);
+        if (saved_floats) *saved_floats = (int64_t)rdr::vnrm::saved_floats(t, cot);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_vertex_normal(const rdr_mesh_topology *topology, int scheme, const float *vertices, float *normals, float *saved,
+                      float *scratch, int64_t scratch_floats) {
+    try {
+        g_last_error.clear();
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_vertex_normal");
+        std::lock_guard<std::recursive_mutex> lk(device_lock(t.gpu_index));
+        mip_select(t.gpu_index, "rdr_vertex_normal");
+        rdr::vnrm::forward(t, scheme, vertices, normals, saved, scratch, scratch_floats > 0 ? (size_t)scratch_floats : 0);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_vertex_normal_backward(const rdr_mesh_topology *topology, int scheme, const float *vertices, const float *saved,
+                               const float *d_normals, float *d_vertices, float *scratch, int64_t scratch_floats) {
+    try {
+        g_last_error.clear();
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_vertex_normal_backward");
+        std::lock_guard<std::recursive_mutex> lk(device_lock(t.gpu_index));
+        mip_select(t.gpu_index, "rdr_vertex_normal_backward");
+        rdr::vnrm::backward(t, scheme, vertices, saved, d_normals, d_vertices, scratch, scratch_floats > 0 ? (size_t)scratch_floats : 0);
         return 0;
     } catch (const std::exception &e) {
         set_error(e.what());

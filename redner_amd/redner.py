@@ -501,6 +501,74 @@ def mip_pyramid_backward(d_levels, d_texels, scratch, scratch_floats, height, wi
         raise RuntimeError('redner.mip_pyramid_backward: ' + _capi.last_error())
 
 
+class NormalWeighting(enum.IntEnum):
+    """Not in the reference's module: rdr_normal_weighting, the weighting_scheme strings of pyredner.compute_vertex_normal."""
+    max = 0
+    cotangent = 1
+
+
+class mesh_topology:
+    """Not in the reference's module: the native plan of one connectivity (rdr_mesh_topology_create, csrc/vertex_normal.h): the
+    corners incident to every vertex in ascending corner id.  indices: int_ptr of [num_triangles, 3] int32 in the memory the
+    later calls' tensors live in.  Belongs to the library that was loaded when it was made and is destroyed with it on
+    collection (or by destroy())."""
+
+    def __init__(self, indices, num_triangles, num_vertices, use_gpu, gpu_index):
+        self.lib, self.handle = _capi.lib(), None
+        self.num_triangles, self.num_vertices = int(num_triangles), int(num_vertices)
+        self.use_gpu, self.gpu_index = bool(use_gpu), int(gpu_index)
+        _use_torch_stream(self.lib, use_gpu, gpu_index)
+        self.handle = self.lib.rdr_mesh_topology_create(_addr(indices) or None, self.num_triangles, self.num_vertices,
+                                                        int(self.use_gpu), self.gpu_index)
+        if not self.handle:
+            raise RuntimeError('redner.mesh_topology: ' + _capi.last_error())
+
+    def destroy(self):
+        if self.handle:
+            self.lib.rdr_mesh_topology_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def _error(self, what):
+        return RuntimeError('redner.%s: %s' % (what, self.lib.rdr_last_error().decode()))
+
+    def read(self):
+        """(offsets [V + 1], corners [3 T]) as lists: the rows of the plan (tests)."""
+        offsets, corners = (C.c_int * (self.num_vertices + 1))(), (C.c_int * max(3 * self.num_triangles, 1))()
+        if self.lib.rdr_mesh_topology_read(self.handle, offsets, corners) != 0:
+            raise self._error('mesh_topology.read')
+        return list(offsets), list(corners)[:3 * self.num_triangles]
+
+    def scratch(self, scheme):
+        """floats of (forward scratch, backward scratch, saved) for a weighting scheme (rdr_vertex_normal_scratch)."""
+        counts = [C.c_int64(0) for _ in range(3)]
+        if self.lib.rdr_vertex_normal_scratch(self.handle, int(scheme), *[C.byref(c) for c in counts]) != 0:
+            raise self._error('mesh_topology.scratch')
+        return tuple(int(c.value) for c in counts)
+
+
+def vertex_normal(topology, scheme, vertices, normals, saved, scratch, scratch_floats):
+    """Not in the reference's module (its compute_vertex_normal is torch code, pyredner/shape.py): rdr_vertex_normal.  float_ptr
+    arguments; writes normals [V, 3] and saved.  Ordered on the current torch stream, not synchronised."""
+    _use_torch_stream(topology.lib, topology.use_gpu, topology.gpu_index)
+    if topology.lib.rdr_vertex_normal(topology.handle, int(scheme), _addr(vertices), _addr(normals), _addr(saved),
+                                      _addr(scratch) or None, int(scratch_floats)) != 0:
+        raise topology._error('vertex_normal')
+
+
+def vertex_normal_backward(topology, scheme, vertices, saved, d_normals, d_vertices, scratch, scratch_floats):
+    """Not in the reference's module: rdr_vertex_normal_backward.  Writes every element of d_vertices [V, 3]."""
+    _use_torch_stream(topology.lib, topology.use_gpu, topology.gpu_index)
+    if topology.lib.rdr_vertex_normal_backward(topology.handle, int(scheme), _addr(vertices), _addr(saved), _addr(d_normals),
+                                               _addr(d_vertices), _addr(scratch) or None, int(scratch_floats)) != 0:
+        raise topology._error('vertex_normal_backward')
+
+
 def _use_torch_stream(lib, use_gpu, gpu_index=None):
     """The library orders its launches on the calling thread's CURRENT torch stream OF THE SCENE'S DEVICE (rdr_set_stream):
     tensors produced under `with torch.cuda.stream(s):` are read after their producers without a device-wide

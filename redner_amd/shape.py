@@ -1,0 +1,141 @@
+"""Smooth vertex normals (pyredner/shape.py: compute_vertex_normal) on the native kernels, with a vertex gradient.
+
+    topology = MeshTopology(indices, num_vertices)                   # once per connectivity
+    for it in range(steps):
+        shape.normals = compute_vertex_normal(vertices, indices, 'max', topology=topology)
+        loss(render(scene)).backward()                               # vertices.grad: the geometric part + the normals' part
+
+The meaning is the reference's (csrc/vertex_normal.h restates it):
+
+  * 'max': every corner adds  n * sin(angle) / (|e1| |e2|)  to its vertex (n: the face's unit normal, e1, e2: the corner's
+    sides); the sum is normalised, or (0, 0, 1) where it is zero (an isolated vertex).
+  * 'cotangent': corner i adds (v[i+2] - v[i+1]) * cot(angle_i) to vertex i + 1 and subtracts it from vertex i + 2; the sum is
+    turned to the side of the 'max' normal and normalised if it is longer than 0.05, otherwise the 'max' normal is the result.
+  * per-corner terms in fp32, per-vertex sums in fp64 in ascending corner id 3 f + k, rounded once: a function of `indices`
+    only, so the normals AND the gradient are bitwise reproducible (the reference's scatter_add_ is fp32 atomics on a GPU).
+  * the gradient of a degenerate corner or face, and of a vertex that takes (0, 0, 1), is 0 where the reference returns NaN.
+
+What depends on `indices` only (validation, the rows of corners per vertex) is a `MeshTopology`, built once; without one,
+compute_vertex_normal keeps the plans of the last 8 index tensors it saw.
+
+There is no torch fall-back: the tensors' memory goes to the loaded native library.  CPU tensors are accepted by the CPU
+debugging harness only (the test-suite loads it); the product library raises for them.
+"""
+import collections
+import threading
+
+import torch
+
+from . import redner as _default_backend
+
+SCHEMES = {'max': 0, 'cotangent': 1}
+PLAN_CACHE_SIZE = 8
+
+
+def _place(t):
+    use_gpu = t.device.type == 'cuda'
+    index = t.device.index if t.device.index is not None else (torch.cuda.current_device() if use_gpu else 0)
+    return use_gpu, index
+
+
+class MeshTopology:
+    """The plan of one connectivity: indices [T, 3] (int32, or int64: converted once here) validated against num_vertices and
+    turned into the rows of corners per vertex, on the indices' device.  Raises RuntimeError for an index outside
+    [0, num_vertices).  Owns the native plan and destroys it on collection."""
+
+    def __init__(self, indices, num_vertices, backend=None):
+        rd = backend or _default_backend
+        if not isinstance(indices, torch.Tensor) or indices.dim() != 2 or indices.shape[1] != 3:
+            raise RuntimeError('MeshTopology: indices must be a [T, 3] tensor, got %s' % (tuple(getattr(indices, 'shape', ())),))
+        if indices.dtype == torch.int64:
+            # (values beyond int32 stay out of range instead of wrapping into it)
+            indices = indices.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+        if indices.dtype != torch.int32:
+            raise RuntimeError('MeshTopology: int32 or int64 indices only')
+        indices = indices.detach().contiguous()
+        self.num_vertices, self.num_triangles, self.device = int(num_vertices), int(indices.shape[0]), indices.device
+        use_gpu, index = _place(indices)
+        self.native = rd.mesh_topology(rd.int_ptr(indices.data_ptr()), self.num_triangles, self.num_vertices, use_gpu, index)
+        self.rd = rd
+
+    def rows(self):
+        """(offsets, corners): vertex v sums the corners corners[offsets[v]:offsets[v + 1]] in that order (corner 3 f + k)."""
+        return self.native.read()
+
+
+class VertexNormals(torch.autograd.Function):
+    """vertices [V, 3] -> normals [V, 3].  One native call forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, vertices, topology, scheme):
+        rd = topology.rd
+        if vertices.dim() != 2 or tuple(vertices.shape) != (topology.num_vertices, 3):
+            raise RuntimeError('compute_vertex_normal: vertices must be [%d, 3], got %s' % (topology.num_vertices, tuple(vertices.shape)))
+        if vertices.dtype != torch.float32:
+            raise RuntimeError('compute_vertex_normal: fp32 vertices only')
+        if vertices.device != topology.device:
+            raise RuntimeError('compute_vertex_normal: vertices are on %s, the topology on %s' % (vertices.device, topology.device))
+        v = vertices.detach().contiguous()
+        n_fwd, _, n_saved = topology.native.scratch(scheme)
+        normals = torch.empty_like(v)
+        saved = torch.empty(max(n_saved, 1), dtype=torch.float32, device=v.device)
+        scratch = torch.empty(max(n_fwd, 1), dtype=torch.float32, device=v.device)
+        rd.vertex_normal(topology.native, scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(normals.data_ptr()),
+                         rd.float_ptr(saved.data_ptr()), rd.float_ptr(scratch.data_ptr()), n_fwd)
+        ctx.topology, ctx.scheme = topology, scheme
+        ctx.save_for_backward(v, saved)
+        ctx.set_materialize_grads(False)
+        return normals
+
+    @staticmethod
+    def backward(ctx, d_normals):
+        if d_normals is None:
+            return None, None, None
+        topology, rd = ctx.topology, ctx.topology.rd
+        v, saved = ctx.saved_tensors
+        g = d_normals.to(device=v.device, dtype=torch.float32).contiguous()
+        n_bwd = topology.native.scratch(ctx.scheme)[1]
+        d_vertices = torch.empty_like(v)
+        scratch = torch.empty(max(n_bwd, 1), dtype=torch.float32, device=v.device)
+        rd.vertex_normal_backward(topology.native, ctx.scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(saved.data_ptr()),
+                                  rd.float_ptr(g.data_ptr()), rd.float_ptr(d_vertices.data_ptr()), rd.float_ptr(scratch.data_ptr()),
+                                  n_bwd)
+        return d_vertices, None, None
+
+
+# the plans compute_vertex_normal made itself: key -> (the indices tensor, MeshTopology).  The key names the tensor's memory and
+# version; the entry keeps the tensor alive, so its address cannot be handed to another tensor while the entry exists.
+_plans = collections.OrderedDict()
+_plans_lock = threading.Lock()          # compute_vertex_normal may be called from several threads (one per device)
+
+
+def _cached_topology(indices, num_vertices, rd):
+    from . import _capi
+    if not isinstance(indices, torch.Tensor):
+        raise RuntimeError('compute_vertex_normal: indices must be a [T, 3] tensor')
+    key = (indices.data_ptr(), indices._version, tuple(indices.shape), tuple(indices.stride()), indices.dtype, str(indices.device),
+           int(num_vertices), id(rd), _capi.library_path())
+    with _plans_lock:
+        hit = _plans.get(key)
+        if hit is not None:
+            _plans.move_to_end(key)
+            return hit[1]
+    topology = MeshTopology(indices, num_vertices, backend=rd)          # (outside the lock: it synchronises a device)
+    with _plans_lock:
+        _plans[key] = (indices, topology)
+        while len(_plans) > PLAN_CACHE_SIZE:
+            _plans.popitem(last=False)
+    return topology
+
+
+def compute_vertex_normal(vertices, indices, weighting_scheme='max', topology=None, backend=None):
+    """pyredner.compute_vertex_normal: the [V, 3] fp32 vertex normals of a mesh (contiguous, on the vertices' device),
+    differentiable with respect to `vertices`.  weighting_scheme: 'max' or 'cotangent'.  topology: the MeshTopology of
+    `indices` (then `indices` is not looked at); None = one is made and kept for the next call with the same index tensor."""
+    if weighting_scheme not in SCHEMES:
+        raise ValueError('Unknown weighting scheme: {}'.format(weighting_scheme))
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError('compute_vertex_normal: vertices must be a [V, 3] tensor')
+    if topology is None:
+        topology = _cached_topology(indices, int(vertices.shape[0]), backend or _default_backend)
+    return VertexNormals.apply(vertices, topology, SCHEMES[weighting_scheme])
