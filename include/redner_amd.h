@@ -387,6 +387,20 @@ int rdr_debug_bvh_check(const rdr_scene *scene);
  * text, for the build-order parity test against the reference (tests/test_edge_build.py). */
 int rdr_debug_dump_edges(const rdr_scene *scene, const char *path);
 
+/* Test hook: the traversal launch the library would make (csrc/trace_plan.h: the rules) for a queue of num_rays rays on a
+ * hierarchy of num_nodes node records whose binary / 4-wide walks need stack_need / wide_stack_need stack entries (has_wide:
+ * the 4-wide records exist); `counting` as in rdr_trace_stats_enable; tuning NULL = every default and the environment.
+ *   out[0] form: 0 trace_wide_kernel, 1 trace_refill_kernel, 2 trace_kernel      out[1] stack entries of the instantiation
+ *   out[2] 16-bit stack entries   out[3] hierarchy top staged in LDS   out[4] rays handed out in refill_order (refill)
+ *   out[5] counting variant       out[6] workgroups                    out[7 .. 9] rays per lane, idle lanes, steps (refill; else 0)
+ * rdr_debug_scene_trace_plan: the same for the hierarchy of a Scene, i.e. what rdr_scene_trace(scene, ..., num_rays, any_hit)
+ * launches.  Host arithmetic only (no device is touched).  Return 0, or 1 (rdr_last_error) for num_rays <= 0, a negative
+ * size or a NULL out / scene. */
+int rdr_debug_trace_plan(int num_nodes, int stack_need, int has_wide, int wide_stack_need, int num_rays, int any_hit, int coherent,
+                         int counting, const rdr_tuning *tuning, int32_t *out /* [10] */);
+int rdr_debug_scene_trace_plan(const rdr_scene *scene, int num_rays, int any_hit, int coherent, int counting,
+                               const rdr_tuning *tuning, int32_t *out /* [10] */);
+
 /* The library is built twice from the same sources (__graft_entry__.build_native):
  *   libredner_amd.so        the stage kernels call the DEVICE's own sin / cos / atan2 / atan / acos / log / pow (ocml): the
  *                           default, +1 ... 3 % throughput; every result is an equally valid sample of the same estimator, and

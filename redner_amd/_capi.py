@@ -153,7 +153,7 @@ EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_textu
            'rdr_mip_num_levels', 'rdr_mip_backward_scratch', 'rdr_mip_tiled_stages', 'rdr_mip_pyramid',
            'rdr_mip_pyramid_backward',
            'rdr_mesh_topology_create', 'rdr_mesh_topology_destroy', 'rdr_mesh_topology_read', 'rdr_vertex_normal_scratch',
-           'rdr_vertex_normal', 'rdr_vertex_normal_backward')
+           'rdr_vertex_normal', 'rdr_vertex_normal_backward', 'rdr_debug_trace_plan', 'rdr_debug_scene_trace_plan')
 
 _lib = None
 _lib_path = None
@@ -242,6 +242,10 @@ def load(path=None):
     lib.rdr_vertex_normal_backward.restype = C.c_int
     lib.rdr_vertex_normal_backward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int64]
+    lib.rdr_debug_trace_plan.restype = C.c_int
+    lib.rdr_debug_trace_plan.argtypes = [C.c_int] * 8 + [C.POINTER(Tuning), C.c_void_p]
+    lib.rdr_debug_scene_trace_plan.restype = C.c_int
+    lib.rdr_debug_scene_trace_plan.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(Tuning), C.c_void_p]
     _lib, _lib_path = lib, path
     return lib
 

@@ -2,6 +2,7 @@
 #include "../../include/redner_amd.h"
 #include "render.h"
 #include "tuning.h"
+#include "trace_plan.h"
 #include "edges.h"
 #include "deferred.h"
 #include "mipmap.h"
@@ -430,6 +431,33 @@ int rdr_scene_trace(const rdr_scene *scene, const float *rays, int32_t *hits, in
         set_error(e.what());
         return 1;
     }
+}
+
+/* Test hooks: the launch exec::trace() would make (trace_plan.h) -- for stated sizes of a hierarchy, and for a Scene's own.
+ * Host arithmetic only: no device is selected or touched. */
+static int write_trace_plan(const exec::TraceFacts &facts, int num_rays, int any_hit, int coherent, int counting,
+                            const rdr_tuning *tuning, int32_t *out) {
+    try {
+        g_last_error.clear();
+        if (num_rays <= 0 || !out || facts.num_nodes < 0 || facts.stack_need < 0 || facts.wide_stack_need < 0)
+            throw std::runtime_error("rdr_debug_trace_plan: bad arguments");
+        const exec::TracePlan p = exec::plan_trace(facts, num_rays, any_hit != 0, coherent != 0, counting != 0, rdr::resolve_tuning(tuning));
+        const int32_t v[10] = {(int32_t)p.form, p.stack, p.short_index, p.stage_top, p.sorted, p.counting, p.blocks, p.rays_per_lane, p.idle_min, p.steps};
+        std::memcpy(out, v, sizeof(v));
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+int rdr_debug_trace_plan(int num_nodes, int stack_need, int has_wide, int wide_stack_need, int num_rays, int any_hit, int coherent,
+                         int counting, const rdr_tuning *tuning, int32_t *out) {
+    return write_trace_plan(exec::TraceFacts{num_nodes, stack_need, wide_stack_need, has_wide != 0}, num_rays, any_hit, coherent, counting, tuning, out);
+}
+int rdr_debug_scene_trace_plan(const rdr_scene *scene, int num_rays, int any_hit, int coherent, int counting, const rdr_tuning *tuning,
+                               int32_t *out) {
+    if (!scene) { set_error("rdr_debug_scene_trace_plan: bad arguments"); return 1; }
+    return write_trace_plan(exec::trace_facts(reinterpret_cast<const rdr::Scene *>(scene)->bvh), num_rays, any_hit, coherent, counting, tuning, out);
 }
 
 /* Test hook: the library's transcendental routines (libm_exact.h) evaluated by a kernel on `n` arguments (HOST pointers;

@@ -4,18 +4,20 @@
 // One ray per lane, 256-thread workgroups, per-lane traversal stack in an LDS column (16-bit entries when the
 // hierarchy allows); nodes and triangles are read through L1/L2 (the whole bunny_box hierarchy is ~1 MB and lives in
 // the 4 MiB per-XCD L2).  rt::traverse<> is the shared per-ray routine, so results are bit-identical to the
-// brute-force rule in raytri.h.  Three kernels, chosen per launch by exec::trace():
-//   trace_kernel          binary 32-byte records, one ray per lane                       (coherent queues; 2^19 < n < 2^22)
-//   trace_wide_kernel     4-wide 128-byte records, one ray per lane: half the steps      (queues of <= 2^19 rays)
-//   trace_refill_kernel   binary records, idle lanes take the next rays of the wave's    (incoherent queues sized for >= 2^22
-//                         own chunk                                                       lanes)
+// brute-force rule in raytri.h.  Three kernels; exec::trace() launches the one that exec::plan_trace() picks for the queue
+// (../trace_plan.h: the rules, their thresholds and the measurements behind them):
+//   trace_kernel          binary 32-byte records, one ray per lane                       (otherwise)
+//   trace_wide_kernel     4-wide 128-byte records, one ray per lane: half the steps      (small queues)
+//   trace_refill_kernel   binary records, idle lanes take the next rays of the wave's own chunk   (large incoherent queues)
 // Measured numbers, what bounds a launch and the loop shapes that were tried and rejected are in DESIGN.md section 3
 // ("Traversal kernel", "Round 3") and profiles/r1_notes.md, r2_notes.md, r3_notes.md.
 #include "exec.h"
 #include "../tuning.h"
+#include "../trace_plan.h"
 #include <algorithm>
 #include <cstring>
 #include <map>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -668,159 +670,81 @@ void trace_stats_collect() {           // call between render() calls: every wor
     }
 }
 
+namespace {
+// {nodes, tris} of the query type at [0, 1] of its base, its ray tally at [4] (closest) / [3] relative to base + 2 (any)
+unsigned long long *counter_base(bool any) {
+    std::lock_guard<std::mutex> lk(g_stats_lock);
+    if (!g_counters) {
+        g_counters = (unsigned long long *)dmalloc(64);
+        check(hipMemset(g_counters, 0, 64), "hipMemset");        // synchronous: another worker's launch may be next
+    }
+    return any ? g_counters + 2 : g_counters;
+}
+
+// A plan's runtime values as template arguments: the helper of a family calls `f` with the constants of one of its instantiations.
+// These branches ARE the set of kernels in the code object: 2 x 2 x 6 wide, 2 x 2 x 4 refilling, 2 x 2 x 4 x 2 x 2 plain.
+template <bool V> using Bool = std::bool_constant<V>;
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F> void by_bool(bool b, F f) { if (b) f(Bool<true>{}); else f(Bool<false>{}); }
+template <int... TIERS, class F> void by_stack(int stack, F f) {
+    if (!((stack == TIERS && (f(Int<TIERS>{}), true)) || ...)) throw std::logic_error("trace: the plan names a stack tier its kernel family does not have");
+}
+template <class F> void wide_case(const TracePlan &p, bool any, F f) {
+    by_bool(any, [&](auto a) { by_bool(p.counting, [&](auto c) { by_stack<12, 16, 20, 24, 32, kWideStackMax>(p.stack, [&](auto st) { f(a, c, st); }); }); });
+}
+template <class F> void refill_case(const TracePlan &p, bool any, F f) {      // 16-bit entries: the 24-entry tier only
+    by_bool(any, [&](auto a) { by_bool(p.sorted, [&](auto so) {
+        if (p.short_index) by_stack<24>(p.stack, [&](auto st) { f(a, st, Bool<true>{}, so); });
+        else by_stack<kHybridLds, 32, rt::kTraverseStack>(p.stack, [&](auto st) { f(a, st, Bool<false>{}, so); });
+    }); });
+}
+template <class F> void plain_case(const TracePlan &p, bool any, F f) {
+    by_bool(any, [&](auto a) { by_bool(p.counting, [&](auto c) { by_stack<16, 24, 32, rt::kTraverseStack>(p.stack, [&](auto st) {
+        by_bool(p.short_index, [&](auto sh) { by_bool(p.stage_top, [&](auto top) { f(a, c, st, sh, top); }); }); }); }); });
+}
+template <bool SHORT> using StackIndex = std::conditional_t<SHORT, unsigned short, int>;
+}
+
+// facts -> plan (trace_plan.h: every rule, with the measurement behind it) -> the planned kernel -> statistics
 void trace(const rt::BvhD &bvh, const rt::RayRec *rays, rt::HitRec *hits, Count cnt, bool any, bool coherent) {
     const int n = cnt.upper;
     const int *n_dev = cnt.dev;
     if (n <= 0) return;
     TraceStats &st = trace_stats();
     hipStream_t s = ctx().stream;
-    int blocks = (n + 255) / 256;
+    const TracePlan plan = plan_trace(trace_facts(bvh), n, any, coherent, st.counting, rdr::tuning());
     Pending p{};
     if (st.timing) {
         { std::lock_guard<std::mutex> lk(g_stats_lock); p.a = get_event(); p.b = get_event(); }
         p.any = any;
         check(hipEventRecord(p.a, s), "hipEventRecord");
     }
-    // Staging pays on big queues (closest-hit 0.330 -> 0.321 ms per 956 k rays); on a 256 x 256 frame the 8 KiB copy + barrier per
-    // 256 rays costs more than the L1-hot top levels save (optimisation-loop iteration +2 ms).  RDR_TUNE_TRACE_NO_LDS_TOP: never.
-    const rdr::Tuning &tune = rdr::tuning();
-    const bool stage_top = !tune.has(RDR_TUNE_TRACE_NO_LDS_TOP) && n >= (1 << 18);
-    // Which form of the hierarchy: queues of up to RDR_WIDE_MAX rays (default 2^19) walk the 4-wide records (measured,
-    // tools/trace_ab.py, profiles/r3_notes.md: half the dependent steps per ray pays where a launch is one or two waves per
-    // SIMD -- closest-hit 0.119 -> 0.102 ms, any-hit 0.078 -> 0.066 ms per 65 k / 50 k rays; on queues of a million rays and
-    // more both forms issue the same number of vector instructions per wave and the binary records, at 8 instead of 5 waves
-    // per SIMD, are 0-10 % ahead).  RDR_TUNE_TRACE_BINARY: never the wide records.
-    const bool wide_allowed = !tune.has(RDR_TUNE_TRACE_BINARY);
-    const int wide_max = tune.wide_max;
-    if (wide_allowed && bvh.wide != nullptr && bvh.wide_stack_need <= 48 && n <= wide_max) {
-        unsigned long long *ctr = nullptr;
-        if (st.counting) {
-            std::lock_guard<std::mutex> lk(g_stats_lock);
-            if (!g_counters) {
-                g_counters = (unsigned long long *)dmalloc(64);
-                check(hipMemset(g_counters, 0, 64), "hipMemset");
-            }
-            ctr = any ? g_counters + 2 : g_counters;
-        }
-#define RDR_WIDE_LAUNCH(ANY_, COUNT_, STACK_) \
-        hipLaunchKernelGGL((trace_wide_kernel<ANY_, COUNT_, STACK_>), dim3(blocks), dim3(256), 0, s, bvh, rays, hits, n, n_dev, ctr)
-        const int wneed = bvh.wide_stack_need;
-#define RDR_WIDE_BY_STACK(ANY_, COUNT_)                                        \
-        do {                                                                   \
-            if (wneed <= 12) RDR_WIDE_LAUNCH(ANY_, COUNT_, 12);  \
-            else if (wneed <= 16) RDR_WIDE_LAUNCH(ANY_, COUNT_, 16); \
-            else if (wneed <= 20) RDR_WIDE_LAUNCH(ANY_, COUNT_, 20); \
-            else if (wneed <= 24) RDR_WIDE_LAUNCH(ANY_, COUNT_, 24); \
-            else if (wneed <= 32) RDR_WIDE_LAUNCH(ANY_, COUNT_, 32); \
-            else RDR_WIDE_LAUNCH(ANY_, COUNT_, 48);                            \
-        } while (0)
-        if (st.counting) { if (any) RDR_WIDE_BY_STACK(true, true); else RDR_WIDE_BY_STACK(false, true); }
-        else { if (any) RDR_WIDE_BY_STACK(true, false); else RDR_WIDE_BY_STACK(false, false); }
-#undef RDR_WIDE_BY_STACK
-#undef RDR_WIDE_LAUNCH
-        check(hipGetLastError(), "trace launch");
-        if (st.timing) check(hipEventRecord(p.b, s), "hipEventRecord");
-        std::lock_guard<std::mutex> lk(g_stats_lock);
-        if (st.timing) g_pending.push_back(p);
-        (any ? st.any_launches : st.closest_launches)++;
-        if (!st.counting) (any ? st.any_rays : st.closest_rays) += (uint64_t)n;
-        return;
+    const dim3 grid(plan.blocks), block(256);
+    unsigned long long *ctr = plan.counting ? counter_base(any) : nullptr;
+    switch (plan.form) {
+    case TraceForm::Wide:
+        wide_case(plan, any, [&](auto a, auto c, auto stack) {
+            hipLaunchKernelGGL((trace_wide_kernel<a, c, stack>), grid, block, 0, s, bvh, rays, hits, n, n_dev, ctr);
+        });
+        break;
+    case TraceForm::Refill:
+        refill_case(plan, any, [&](auto a, auto stack, auto sh, auto sorted) {
+            hipLaunchKernelGGL((trace_refill_kernel<a, stack, StackIndex<sh>, sorted>), grid, block, 0, s, bvh, rays, hits, n, n_dev,
+                               plan.rays_per_lane, plan.idle_min, plan.steps, plan.sort_mode);
+        });
+        break;
+    case TraceForm::Plain:
+        plain_case(plan, any, [&](auto a, auto c, auto stack, auto sh, auto top) {
+            hipLaunchKernelGGL((trace_kernel<a, c, stack, StackIndex<sh>, top>), grid, block, 0, s, bvh, rays, hits, n, n_dev, ctr);
+        });
+        break;
     }
-    // lanes refilled from the wave's own chunk of the queue (see trace_refill_kernel): queues sized for >= 2^22 lanes that the
-    // caller does not mark coherent.  (The queue's host-side bound decides: a launch sized for 2^22 lanes -- four samples of a
-    // 1024 x 1024 frame, the edge sub-paths' two lanes per slot -- still holds 1.5-3.3 M rays after the compactions; choosing the
-    // rays per lane in the kernel from the actual count was measured too and is slower, 61.8 vs 62.5 Msamples/s.)
-    // rdr_tuning: RDR_TUNE_REFILL_OFF never; refill_* those parameters; RDR_TUNE_REFILL_ALL every queue (tools/trace_ab.py).
-    const bool refill_off = tune.has(RDR_TUNE_REFILL_OFF), refill_all = tune.has(RDR_TUNE_REFILL_ALL);
-    const int refill_k = refill_off ? 0 : ((refill_all || (!coherent && n >= (1 << 22))) ? tune.refill_k : 0);
-    if (refill_k >= 1 && !st.counting && bvh.stack_need <= rt::kTraverseStack) {
-        const int idle_min = tune.refill_idle, steps = tune.refill_steps;
-        const int wg_rays = 4 * 64 * refill_k;
-        const int rblocks = (int)(((long long)n + wg_rays - 1) / wg_rays);
-        const int k_arg = refill_k;
-        const int sort_mode = tune.refill_sort;        // rdr_tuning::refill_order: 0 queue order, 1 octant (default), 2 octant x axis
-        const bool small = bvh.num_nodes < 65536 && bvh.stack_need <= 24;
-        // big hierarchies (int entries): 32 entries where that covers the tree -- 40 KiB of LDS per workgroup instead of 49: four
-        // workgroups per CU instead of three (a hierarchy beyond the L2 is latency-bound: more waves, profiles/r6_notes.md)
-        const bool mid32 = !small && bvh.stack_need <= 32;
-        // ... and the hybrid stack (16 LDS entries + scratch: six workgroups per CU) for every hierarchy too big for the 16-bit
-        // column: 0.92 M triangles 2.39 -> 2.73, 3.7 M 2.02 -> 2.33 G rays/s against the 32-entry tier.  RDR_TRACE_HYBRID=0: the tiers.
-        static const bool hybrid_on = [] { const char *e = std::getenv("RDR_TRACE_HYBRID"); return !(e && e[0] == '0'); }();
-        const bool hybrid = !small && hybrid_on;
-#define RDR_REFILL_LAUNCH(ANY_, STACK_, IDX_, SORT_) \
-        hipLaunchKernelGGL((trace_refill_kernel<ANY_, STACK_, IDX_, SORT_>), dim3(rblocks), dim3(256), 0, s, bvh, rays, hits, n, n_dev, k_arg, idle_min, steps, sort_mode)
-        const bool sort_on = sort_mode > 0 && k_arg == 4;
-        if (sort_on) {
-            if (any && small) RDR_REFILL_LAUNCH(true, 24, unsigned short, true);
-            else if (any && hybrid) RDR_REFILL_LAUNCH(true, 16, int, true);
-            else if (any && mid32) RDR_REFILL_LAUNCH(true, 32, int, true);
-            else if (any) RDR_REFILL_LAUNCH(true, rt::kTraverseStack, int, true);
-            else if (small) RDR_REFILL_LAUNCH(false, 24, unsigned short, true);
-            else if (hybrid) RDR_REFILL_LAUNCH(false, 16, int, true);
-            else if (mid32) RDR_REFILL_LAUNCH(false, 32, int, true);
-            else RDR_REFILL_LAUNCH(false, rt::kTraverseStack, int, true);
-        } else {
-            if (any && small) RDR_REFILL_LAUNCH(true, 24, unsigned short, false);
-            else if (any && hybrid) RDR_REFILL_LAUNCH(true, 16, int, false);
-            else if (any && mid32) RDR_REFILL_LAUNCH(true, 32, int, false);
-            else if (any) RDR_REFILL_LAUNCH(true, rt::kTraverseStack, int, false);
-            else if (small) RDR_REFILL_LAUNCH(false, 24, unsigned short, false);
-            else if (hybrid) RDR_REFILL_LAUNCH(false, 16, int, false);
-            else if (mid32) RDR_REFILL_LAUNCH(false, 32, int, false);
-            else RDR_REFILL_LAUNCH(false, rt::kTraverseStack, int, false);
-        }
-#undef RDR_REFILL_LAUNCH
-        check(hipGetLastError(), "trace launch");
-        if (st.timing) check(hipEventRecord(p.b, s), "hipEventRecord");
-        std::lock_guard<std::mutex> lk(g_stats_lock);
-        if (st.timing) g_pending.push_back(p);
-        (any ? st.any_launches : st.closest_launches)++;
-        (any ? st.any_rays : st.closest_rays) += (uint64_t)n;
-        return;
-    }
-#define RDR_TRACE_LAUNCH(ANY_, COUNT_, STACK_, ctr)                                                                          \
-    do {                                                                                                                     \
-        if (bvh.num_nodes < 65536 && stage_top)                                                                              \
-            hipLaunchKernelGGL((trace_kernel<ANY_, COUNT_, STACK_, unsigned short, true>), dim3(blocks), dim3(256), 0, s, bvh, rays, hits, n, n_dev, ctr); \
-        else if (bvh.num_nodes < 65536)                                                                                      \
-            hipLaunchKernelGGL((trace_kernel<ANY_, COUNT_, STACK_, unsigned short, false>), dim3(blocks), dim3(256), 0, s, bvh, rays, hits, n, n_dev, ctr); \
-        else if (stage_top)                                                                                                  \
-            hipLaunchKernelGGL((trace_kernel<ANY_, COUNT_, STACK_, int, true>), dim3(blocks), dim3(256), 0, s, bvh, rays, hits, n, n_dev, ctr);            \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((trace_kernel<ANY_, COUNT_, STACK_, int, false>), dim3(blocks), dim3(256), 0, s, bvh, rays, hits, n, n_dev, ctr);            \
-    } while (0)
-#define RDR_TRACE_BY_STACK(ANY_, COUNT_, ctr)                                  \
-    do {                                                                       \
-        if (bvh.stack_need <= 16) RDR_TRACE_LAUNCH(ANY_, COUNT_, 16, ctr);      \
-        else if (bvh.stack_need <= 24) RDR_TRACE_LAUNCH(ANY_, COUNT_, 24, ctr); \
-        else if (bvh.stack_need <= 32) RDR_TRACE_LAUNCH(ANY_, COUNT_, 32, ctr); \
-        else RDR_TRACE_LAUNCH(ANY_, COUNT_, rt::kTraverseStack, ctr);          \
-    } while (0)
-    if (st.counting) {
-        {
-            std::lock_guard<std::mutex> lk(g_stats_lock);
-            if (!g_counters) {
-                g_counters = (unsigned long long *)dmalloc(64);
-                check(hipMemset(g_counters, 0, 64), "hipMemset");        // synchronous: another worker's launch may be next
-            }
-        }
-        // counters: {nodes, tris} of this query type at [0, 1], its ray tally at [4] (closest) / [3] relative to base + 2 (any)
-        if (any) RDR_TRACE_BY_STACK(true, true, g_counters + 2);
-        else RDR_TRACE_BY_STACK(false, true, g_counters);
-    } else {
-        if (any) RDR_TRACE_BY_STACK(true, false, (unsigned long long *)nullptr);
-        else RDR_TRACE_BY_STACK(false, false, (unsigned long long *)nullptr);
-    }
-#undef RDR_TRACE_BY_STACK
-#undef RDR_TRACE_LAUNCH
     check(hipGetLastError(), "trace launch");
-    if (st.timing) {
-        check(hipEventRecord(p.b, s), "hipEventRecord");
-    }
+    if (st.timing) check(hipEventRecord(p.b, s), "hipEventRecord");
     std::lock_guard<std::mutex> lk(g_stats_lock);
     if (st.timing) g_pending.push_back(p);
     (any ? st.any_launches : st.closest_launches)++;
-    if (!st.counting) (any ? st.any_rays : st.closest_rays) += (uint64_t)n;     // an upper bound; exact tallies come from the counting kernels
+    if (!plan.counting) (any ? st.any_rays : st.closest_rays) += (uint64_t)n;     // an upper bound; exact tallies come from the counting kernels
 }
 
 } // namespace exec

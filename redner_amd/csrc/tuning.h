@@ -26,6 +26,7 @@ struct Tuning {
     int refill_sort = 1;                // 0 queue order, 1 octant, 2 octant x axis (trace.hip)
     int pickh_k = 1, pickh_idle = 8, pickh_steps = 8;
     int stale_event_cap = -1;           // -1 = one entry per edge-ray lane (render.cpp: hp_event_cap)
+    bool trace_hybrid = true;           // trace_refill_kernel's hybrid stack for big hierarchies (trace_plan.h); RDR_TRACE_HYBRID=0: off
     bool has(unsigned f) const { return (flags & f) != 0; }
 };
 
@@ -39,6 +40,7 @@ struct EnvDefaults {
     int refill_k = 0, refill_idle = 0, refill_steps = 0, wide_max = 0, gather_budget = 0, heavy_cap = -1, work_cap = -1;
     double mem_mb = -1.0;
     int refill_order = 0, pickh_k = 0, pickh_idle = 0, pickh_steps = 0;
+    bool trace_hybrid = true;
     EnvDefaults() {
         if (env_set("RDR_NO_OVERLAP") || env_set("RDR_DEBUG_DUMP")) flags |= RDR_TUNE_NO_OVERLAP;
         if (env_set("RDR_FORCE_GENERAL")) flags |= RDR_TUNE_FORCE_GENERAL;
@@ -70,6 +72,7 @@ struct EnvDefaults {
         if (const char *e = env("RDR_GATHER_CAPS")) { int h = 0, w = 0; if (std::sscanf(e, "%d,%d", &h, &w) == 2) { heavy_cap = h; work_cap = w; } }
         if (const char *e = env("RDR_MEM_AVAILABLE_MB")) mem_mb = std::atof(e);
         if (const char *e = env("RDR_REFILL_SORT")) refill_order = std::atoi(e) + 1;
+        if (const char *e = env("RDR_TRACE_HYBRID")) trace_hybrid = e[0] != '0';
         if (const char *e = env("RDR_PICKH_REFILL")) {
             int k = 0, idle = 0, steps = 0;
             const int got = std::sscanf(e, "%d,%d,%d", &k, &idle, &steps);
@@ -107,6 +110,7 @@ inline Tuning resolve_tuning(const rdr_tuning *t) {
     r.pickh_idle = detail::clampi(pick(u.pickh_idle_lanes, e.pickh_idle, 8), 1, 64);
     r.pickh_steps = detail::clampi(pick(u.pickh_steps, e.pickh_steps, 8), 1, 1024);
     r.stale_event_cap = u.stale_event_cap_plus1 > 0 ? u.stale_event_cap_plus1 - 1 : -1;
+    r.trace_hybrid = e.trace_hybrid;
     return r;
 }
 

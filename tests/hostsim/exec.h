@@ -136,6 +136,7 @@ inline void launch_chunked(Count c, const W &w, int = 4, int = 16, int = 8) { la
 // ---- host stand-ins for the hand-written kernels (compact.hip / trace.hip) ----------------------
 #include "bvh.h"
 #include "tuning.h"
+#include "trace_plan.h"
 #include "trace_sim.h"
 namespace exec {
 inline void select_device(int /*use_gpu*/, int /*gpu_index*/) {}
@@ -158,9 +159,12 @@ inline Count compact_dev(const int *in, Count n, int *out, const P &pred, const 
 }
 struct TraceStats { double closest_ms = 0, any_ms = 0, closest_union_ms = 0, any_union_ms = 0; uint64_t closest_launches = 0, any_launches = 0, closest_rays = 0, any_rays = 0, nodes[2] = {0, 0}, tris[2] = {0, 0}, wide_nodes[2] = {0, 0}; bool timing = false, counting = false; };
 inline TraceStats &trace_stats() { static TraceStats s; return s; }
-inline void trace(const rt::BvhD &bvh, const rt::RayRec *rays, rt::HitRec *hits, Count cnt_n, bool any, bool = false) {
+inline void trace(const rt::BvhD &bvh, const rt::RayRec *rays, rt::HitRec *hits, Count cnt_n, bool any, bool coherent = false) {
     const int n = cnt_n.value();
     TraceStats &st = trace_stats();
+    // like the GPU build: the 4-wide records for the queues that trace_plan.h gives them (by the queue's bound, as there)
+    const bool wide = cnt_n.upper > 0 &&
+                      plan_trace(trace_facts(bvh), cnt_n.upper, any, coherent, st.counting, rdr::tuning()).form == TraceForm::Wide;
     rt::Counters cnt{0, 0}, wcnt{0, 0};
     static const bool sim = std::getenv("RDR_TRACE_SIM") != nullptr;
     if (sim) tracesim::launch(bvh, rays, n, any);
@@ -170,10 +174,8 @@ inline void trace(const rt::BvhD &bvh, const rt::RayRec *rays, rt::HitRec *hits,
         if (!(r.tmax < 0.f)) {
             float o[3] = {r.ox, r.oy, r.oz}, d[3] = {r.dx, r.dy, r.dz};
             int stack[rt::kTraverseStack];
-            const bool binary = rdr::tuning().has(RDR_TUNE_TRACE_BINARY);
-            if (bvh.wide && !binary) {            // like the GPU build: the 4-wide records when the hierarchy has them
-                int wstack[64];
-                if (bvh.wide_stack_need > 64) throw std::runtime_error("wide hierarchy deeper than the harness stack");
+            if (wide) {
+                int wstack[kWideStackMax];
                 h = any ? rt::traverse_wide<true>(bvh, o, d, r.tmin, r.tmax, wstack, 1, st.counting ? &wcnt : nullptr)
                         : rt::traverse_wide<false>(bvh, o, d, r.tmin, r.tmax, wstack, 1, st.counting ? &wcnt : nullptr);
             } else

@@ -244,6 +244,57 @@ def test_big_hierarchy_kernel_forms_agree(gpu_backend, tmp_path):
             assert np.array_equal(z['h1'], first['h1']), name
 
 
+def _big_queue(n, seed):
+    """n rays made like BIG_WORKER's: origins in a box around the scene, directions uniform, every 7th slot dead."""
+    g = torch.Generator().manual_seed(seed)
+    o = (torch.rand(n, 3, generator=g) - 0.5) * 1.6
+    d = torch.randn(n, 3, generator=g); d = d / d.norm(dim=1, keepdim=True)
+    rays = torch.zeros(n, 8); rays[:, 0:3] = o; rays[:, 3] = 1e-3; rays[:, 4:7] = d; rays[:, 7] = float('inf')
+    rays[::7, 7] = -1.0
+    return rays
+
+
+@pytest.mark.gpu
+def test_default_selection_by_queue_size(gpu_backend):
+    """The kernels that the DEFAULT thresholds give a queue of 4096, 2^19 + 1 and 2^22 rays (4-wide records / plain binary /
+    refilling, csrc/trace_plan.h) -- the other tests force a form onto small queues.  The shorter queues are prefixes of the
+    longest: the first 4096 slots get the same hits from all three, and those are the brute-force rule's."""
+    from redner_amd import _capi
+    lib = _capi.lib()
+    dev = torch.device('cuda:0')
+    sc = scenes.bunny_box(dev, resolution=(16, 16))
+    args = RenderFunction.serialize_scene(sc, 1, 1, sampler_type=gpu_backend.SamplerType.sobol, device=dev)
+    u = RenderFunction.unpack_args((1, 2), args[0], args[1:])
+    cpu_sc = scenes.bunny_box(torch.device('cpu'), resolution=(16, 16))
+    sizes, head = (4096, (1 << 19) + 1, 1 << 22), 4096
+    forms = []
+    for n in sizes:
+        plan = np.zeros(10, np.int32)
+        assert lib.rdr_debug_scene_trace_plan(u.scene._handle, n, 0, 0, 0, None, plan.ctypes.data_as(ctypes.c_void_p)) == 0
+        forms.append(int(plan[0]))
+    if len(set(forms)) != 3:
+        pytest.skip('the environment forces a kernel family: forms %s for %s rays' % (forms, sizes))
+    assert forms == [0, 2, 1]          # wide, plain, refilling
+    rays = _big_queue(sizes[-1], 5)
+    d_rays = rays.to(dev).contiguous()
+    head_rays = rays[:head].numpy()
+    dead = head_rays[:, 7] < 0
+    assert dead[::7].all() and dead.sum() == (head + 6) // 7
+    ref = _brute_force([s.vertices.detach().numpy() for s in cpu_sc.shapes], [s.indices.numpy() for s in cpu_sc.shapes], head_rays, 0)
+    assert (ref[:, 0] >= 0).sum() > 1000          # the comparison is not vacuous
+    d_hits = torch.empty(sizes[-1], 2, dtype=torch.int32, device=dev)
+    for any_hit in (0, 1):
+        for n in sizes:
+            d_hits[:head].fill_(7)
+            assert lib.rdr_scene_trace(u.scene._handle, d_rays.data_ptr(), d_hits.data_ptr(), n, any_hit) == 0
+            hits = d_hits[:head].cpu().numpy()
+            assert (hits[dead] == -1).all(), (n, any_hit)
+            if any_hit:
+                assert np.array_equal(hits[:, 0] >= 0, ref[:, 0] >= 0), n
+            else:
+                assert np.array_equal(hits, ref), n
+
+
 # ---- the hierarchy the kernels build (bvh_gpu.cpp) ----------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize('builder', ['single_triangle', 'two_triangles', 'bunny_box', 'living_room_standin', 'triangle_soup_large'])
