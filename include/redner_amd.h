@@ -418,6 +418,35 @@ int rdr_libm_exact(void);
  * fn: 0 sin(x), 1 cos(x), 2 atan2(x, y), 3 atan(x), 4 acos(x), 5 log(x), 6 pow(x, y). */
 int rdr_debug_libm(int fn, const double *x, const double *y, double *out, int n);
 
+/* Test hook: the gradient scatter alone.  Builds the gradient store of a gradient render of `scene` into `d_scene` (the struct
+ * rdr_render takes; `job_samples` sizes the replicas of its large tier as pixels x samples of a render would), launches ONE
+ * stage of `num_lanes` lanes in which lane i -- unless active[i] == 0: it returns first, as the lanes of production stages that
+ * have nothing to add do -- makes one call of `op`, and folds the store into the fp32 tensors of `d_scene` (+=, as a render).
+ * All per-lane arrays are HOST memory.
+ *   RDR_SCATTER_ACCUM / _ACCUM_TEXEL / _ACCUM_PLAIN      values[i] is added to element index[i] of the lane's target
+ *   RDR_SCATTER_ACCUM_TRIPLE / _ACCUM_TEXEL_TRIPLE       values[3 i .. 3 i + 2] to elements index[i] .. index[i] + 2
+ *     target[3 i .. 3 i + 2] = (kind, a, b), kind an rdr_scatter_target:
+ *       VERTICES / UVS / NORMALS / COLORS  of shape a            TEXTURE  level b % 8 of texture b / 8 (0 diffuse, 1 specular,
+ *       2 roughness, 3 generic, 4 normal map) of material a      LIGHTS   the intensities, 3 per area light
+ *       CAMERA  field a (the order of rdr_dcamera_desc)          ENVMAP   level b of the environment map's values
+ *   RDR_SCATTER_TRIGRAD_WAVE     target[3 i], target[3 i + 1] = (shape, triangle), shape < 0: nothing; values[33 i ...] = the
+ *                                corner gradients p[3], n[3] (3 doubles each), uv[3] (2 each), c[3] (3 each); `plain` as the
+ *                                lean stages pass it (no uv / colour gradients); `index` is not read
+ *   RDR_SCATTER_POSITIONS_WAVE   the same with values[9 i ...] = p[3]
+ * Every lane, active or not, is checked on the host first: a target that `d_scene` does not ask for or an element, shape or
+ * triangle out of range returns 1 (rdr_last_error) before anything is launched. */
+enum rdr_scatter_op {
+    RDR_SCATTER_ACCUM = 0, RDR_SCATTER_ACCUM_TEXEL, RDR_SCATTER_ACCUM_PLAIN, RDR_SCATTER_ACCUM_TRIPLE,
+    RDR_SCATTER_ACCUM_TEXEL_TRIPLE, RDR_SCATTER_TRIGRAD_WAVE, RDR_SCATTER_POSITIONS_WAVE
+};
+enum rdr_scatter_target {
+    RDR_TARGET_VERTICES = 0, RDR_TARGET_UVS, RDR_TARGET_NORMALS, RDR_TARGET_COLORS, RDR_TARGET_TEXTURE, RDR_TARGET_LIGHTS,
+    RDR_TARGET_CAMERA, RDR_TARGET_ENVMAP
+};
+int rdr_debug_grad_scatter(const rdr_scene *scene, const rdr_dscene_desc *d_scene, uint64_t job_samples, int op, int plain,
+                           int num_lanes, const uint8_t *active, const int32_t *target, const int32_t *index,
+                           const double *values);
+
 #ifdef __cplusplus
 }
 #endif

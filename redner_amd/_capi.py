@@ -153,7 +153,13 @@ EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_textu
            'rdr_mip_num_levels', 'rdr_mip_backward_scratch', 'rdr_mip_tiled_stages', 'rdr_mip_pyramid',
            'rdr_mip_pyramid_backward',
            'rdr_mesh_topology_create', 'rdr_mesh_topology_destroy', 'rdr_mesh_topology_read', 'rdr_vertex_normal_scratch',
-           'rdr_vertex_normal', 'rdr_vertex_normal_backward', 'rdr_debug_trace_plan', 'rdr_debug_scene_trace_plan')
+           'rdr_vertex_normal', 'rdr_vertex_normal_backward', 'rdr_debug_trace_plan', 'rdr_debug_scene_trace_plan',
+           'rdr_debug_grad_scatter')
+
+# rdr_scatter_op / rdr_scatter_target (rdr_debug_grad_scatter)
+SCATTER_ACCUM, SCATTER_ACCUM_TEXEL, SCATTER_ACCUM_PLAIN, SCATTER_ACCUM_TRIPLE, SCATTER_ACCUM_TEXEL_TRIPLE, \
+    SCATTER_TRIGRAD_WAVE, SCATTER_POSITIONS_WAVE = range(7)
+TARGET_VERTICES, TARGET_UVS, TARGET_NORMALS, TARGET_COLORS, TARGET_TEXTURE, TARGET_LIGHTS, TARGET_CAMERA, TARGET_ENVMAP = range(8)
 
 _lib = None
 _lib_path = None
@@ -246,6 +252,9 @@ def load(path=None):
     lib.rdr_debug_trace_plan.argtypes = [C.c_int] * 8 + [C.POINTER(Tuning), C.c_void_p]
     lib.rdr_debug_scene_trace_plan.restype = C.c_int
     lib.rdr_debug_scene_trace_plan.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(Tuning), C.c_void_p]
+    lib.rdr_debug_grad_scatter.restype = C.c_int
+    lib.rdr_debug_grad_scatter.argtypes = [C.c_void_p, C.POINTER(DSceneDesc), C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib, _lib_path = lib, path
     return lib
 

@@ -488,4 +488,23 @@ int rdr_debug_libm(int fn, const double *x, const double *y, double *out, int n)
     }
 }
 
+/* Test hook: the gradient store of a render, one stage that calls the scatter functions, the fold (render.cpp: debug_grad_scatter). */
+int rdr_debug_grad_scatter(const rdr_scene *scene, const rdr_dscene_desc *d_scene, uint64_t job_samples, int op, int plain,
+                           int num_lanes, const uint8_t *active, const int32_t *target, const int32_t *index,
+                           const double *values) {
+    try {
+        g_last_error.clear();
+        if (!scene || !d_scene) throw std::runtime_error("rdr_debug_grad_scatter: scene and d_scene are required");
+        const rdr::Scene &s = *reinterpret_cast<const rdr::Scene *>(scene);
+        std::lock_guard<std::recursive_mutex> lk(device_lock(s.gpu_index));
+        exec::select_device(1, s.gpu_index);
+        use_caller_stream();
+        rdr::debug_grad_scatter(s, *d_scene, (size_t)job_samples, op, plain != 0, num_lanes, active, target, index, values);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
 } // extern "C"

@@ -1150,6 +1150,151 @@ void render(const Scene &scene, const rdr_render_options &opt, float *image, con
     }
 }
 
+// ---- rdr_debug_grad_scatter (include/redner_amd.h): one stage whose lanes call the scatter functions directly --------------
+namespace {
+struct ScatterProbe {
+    int op; bool plain;
+    const unsigned char *active;
+    double *const *dst;            // the add ops: accumulator of the lane's (first) element
+    const int *shape, *tri;        // the two triangle ops
+    const double *val; int width;  // `width` doubles per lane
+    const ShapeD *shapes; const GShape *gshapes;
+    RDR_FN void operator()(int i) const {
+        if (!active[i]) return;    // how the lanes of AdjPrimaryLive / LeanStage leave a partly active wave behind
+        const double *v = val + (size_t)width * i;
+        switch (op) {
+            case RDR_SCATTER_ACCUM: accum(dst[i], v[0]); break;
+            case RDR_SCATTER_ACCUM_TEXEL: accum_texel(dst[i], v[0]); break;
+            case RDR_SCATTER_ACCUM_PLAIN: accum_plain(dst[i], v[0]); break;
+            case RDR_SCATTER_ACCUM_TRIPLE: accum_triple(dst[i], v[0], v[1], v[2]); break;
+            case RDR_SCATTER_ACCUM_TEXEL_TRIPLE: accum_texel_triple(dst[i], v[0], v[1], v[2]); break;
+            case RDR_SCATTER_TRIGRAD_WAVE: {
+                TriGrad g;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    g.p[k] = v3(v[3 * k], v[3 * k + 1], v[3 * k + 2]);
+                    g.n[k] = v3(v[9 + 3 * k], v[10 + 3 * k], v[11 + 3 * k]);
+                    g.uv[k] = v2(v[18 + 2 * k], v[19 + 2 * k]);
+                    g.c[k] = v3(v[24 + 3 * k], v[25 + 3 * k], v[26 + 3 * k]);
+                }
+                scatter_trigrad_wave(shapes, gshapes, shape[i], tri[i], g, plain);
+                break;
+            }
+            default: {
+                const V3 pb[3] = {v3(v[0], v[1], v[2]), v3(v[3], v[4], v[5]), v3(v[6], v[7], v[8])};
+                scatter_positions_wave(shapes, gshapes, shape[i], tri[i], pb);
+                break;
+            }
+        }
+    }
+};
+}
+
+void debug_grad_scatter(const Scene &scene, const rdr_dscene_desc &ds, size_t job_samples, int op, bool plain, int num_lanes,
+                        const uint8_t *active, const int32_t *target, const int32_t *index, const double *values) {
+    const auto bad = [](const std::string &what) { throw std::runtime_error("rdr_debug_grad_scatter: " + what); };
+    if (op < RDR_SCATTER_ACCUM || op > RDR_SCATTER_POSITIONS_WAVE) bad("unknown op");
+    const bool tri_op = op >= RDR_SCATTER_TRIGRAD_WAVE;
+    const int width = op == RDR_SCATTER_TRIGRAD_WAVE ? 33 : op == RDR_SCATTER_POSITIONS_WAVE ? 9 : op >= RDR_SCATTER_ACCUM_TRIPLE ? 3 : 1;
+    if (num_lanes < 0 || num_lanes > (1 << 24)) bad("num_lanes out of range");
+    if (num_lanes > 0 && (!active || !target || !values || (!tri_op && !index))) bad("a per-lane array is missing");
+
+    GradStore grads(scene, ds, job_samples);            // (throws when the DScene does not match the Scene)
+    const size_t n = (size_t)num_lanes;
+    std::vector<double *> h_dst(n, nullptr);
+    std::vector<int> h_shape(n, -1), h_tri(n, 0);
+    if (tri_op) {
+        for (size_t i = 0; i < n; ++i) {
+            const int s = target[3 * i], t = target[3 * i + 1];
+            const std::string lane = " (lane " + std::to_string(i) + ")";
+            if (s >= (int)scene.shapes.size()) bad("shape out of range" + lane);
+            if (s < 0) continue;
+            const ShapeD &sh = scene.shapes[s];
+            if (t < 0 || t >= sh.num_triangles) bad("triangle out of range" + lane);
+            // what the Scene checked when it was built, once more: no corner may point past an accumulator
+            const int nuv = sh.num_uv_vertices > 0 ? sh.num_uv_vertices : sh.num_vertices;
+            const int nn = sh.num_normal_vertices > 0 ? sh.num_normal_vertices : sh.num_vertices;
+            for (int k = 0; k < 3; ++k) {
+                const int vi = scene.h_indices[s][3 * (size_t)t + k];
+                const int ui = sh.uv_indices ? scene.h_uv_indices[s][3 * (size_t)t + k] : vi;
+                const int ni = sh.normal_indices ? scene.h_normal_indices[s][3 * (size_t)t + k] : vi;
+                if (vi < 0 || vi >= sh.num_vertices || (sh.uvs && (ui < 0 || ui >= nuv)) || (sh.normals && (ni < 0 || ni >= nn)))
+                    bad("corner index out of range" + lane);
+            }
+            h_shape[i] = s; h_tri[i] = t;
+        }
+    } else {
+        GEnvmap h_envmap;
+        if (grads.g.envmap) exec::download(&h_envmap, grads.g.envmap, sizeof(GEnvmap));
+        const int elems = width;
+        for (size_t i = 0; i < n; ++i) {
+            const int kind = target[3 * i], a = target[3 * i + 1], b = target[3 * i + 2];
+            const std::string lane = " (lane " + std::to_string(i) + ")";
+            double *acc = nullptr;
+            size_t count = 0;
+            bool whole_block = false;         // the light intensities: one block, not one mirror per tensor
+            switch (kind) {
+                case RDR_TARGET_VERTICES: case RDR_TARGET_UVS: case RDR_TARGET_NORMALS: case RDR_TARGET_COLORS: {
+                    if (a < 0 || a >= (int)grads.h_shapes.size()) bad("shape out of range" + lane);
+                    const GShape &gs = grads.h_shapes[a];
+                    acc = kind == RDR_TARGET_VERTICES ? gs.vertices : kind == RDR_TARGET_UVS ? gs.uvs : kind == RDR_TARGET_NORMALS ? gs.normals : gs.colors;
+                    break;
+                }
+                case RDR_TARGET_TEXTURE: {
+                    if (a < 0 || a >= (int)grads.h_materials.size()) bad("material out of range" + lane);
+                    if (b < 0 || b >= 5 * kMaxMip) bad("texture level out of range" + lane);
+                    const GMaterial &gm = grads.h_materials[a];
+                    const GTex *tex[5] = {&gm.diffuse, &gm.specular, &gm.roughness, &gm.generic, &gm.normal_map};
+                    acc = tex[b / kMaxMip]->texels[b % kMaxMip];
+                    break;
+                }
+                case RDR_TARGET_LIGHTS:
+                    acc = grads.g.light_intensity; count = 3 * scene.lights.size(); whole_block = true;
+                    break;
+                case RDR_TARGET_CAMERA: {
+                    const GCamera &c = grads.g.cam;
+                    double *const field[8] = {c.position, c.look, c.up, c.cam_to_world, c.world_to_cam, c.intrinsic_mat_inv, c.intrinsic_mat, c.distortion};
+                    if (a < 0 || a >= 8) bad("camera field out of range" + lane);
+                    acc = field[a];
+                    break;
+                }
+                case RDR_TARGET_ENVMAP:
+                    if (b < 0 || b >= kMaxMip) bad("texture level out of range" + lane);
+                    if (grads.g.envmap) acc = h_envmap.values.texels[b];
+                    break;
+                default: bad("unknown target" + lane);
+            }
+            if (!acc) bad("the DScene has no such gradient tensor" + lane);
+            if (!whole_block) {
+                bool found = false;
+                for (const GradStore::Pair &p : grads.pairs) if (p.acc == acc) { count = p.count; found = true; break; }
+                if (!found) bad("target is not an accumulator of the store" + lane);
+            }
+            const long long at = index[i];
+            if (at < 0 || (size_t)at + (size_t)elems > count) bad("element out of range" + lane);
+            h_dst[i] = acc + at;
+        }
+    }
+
+    struct Held {                      // released on every path out, also when the launch or a copy throws
+        std::vector<void *> p;
+        void *get(size_t bytes) { p.push_back(nullptr); p.back() = exec::dmalloc(bytes); return p.back(); }
+        ~Held() { exec::device_sync(); for (void *q : p) exec::dfree(q); }
+    } held;
+    unsigned char *d_active = (unsigned char *)held.get(n);
+    double **d_dst = (double **)held.get(sizeof(double *) * n);
+    int *d_shape = (int *)held.get(sizeof(int) * n), *d_tri = (int *)held.get(sizeof(int) * n);
+    double *d_val = (double *)held.get(sizeof(double) * n * width);
+    exec::upload(d_active, active, n);
+    exec::upload(d_dst, h_dst.data(), sizeof(double *) * n);
+    exec::upload(d_shape, h_shape.data(), sizeof(int) * n);
+    exec::upload(d_tri, h_tri.data(), sizeof(int) * n);
+    exec::upload(d_val, values, sizeof(double) * n * width);
+    exec::launch(exec::Count(num_lanes), ScatterProbe{op, plain, d_active, d_dst, d_shape, d_tri, d_val, width, scene.d.shapes, grads.g.shapes});
+    grads.flush();
+    exec::sync();
+}
+
 } // namespace rdr
 
 // Which transcendental functions this build of the stage kernels calls (include/redner_amd.h: rdr_libm_exact)

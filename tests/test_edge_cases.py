@@ -296,10 +296,10 @@ def _many_patches(device):
     return Scene(cam, shapes + [light], mats, [scenes.AreaLight(12, torch.tensor([20.0, 20.0, 20.0]))])
 
 
-def test_gradient_store_spills_into_the_large_tier_hostsim(hostsim_backend):
+def _spills_into_the_large_tier(backend, device):
     if not oracle_util.oracle_available():
         pytest.skip('oracle not built')
-    img, grads = _run(hostsim_backend, torch.device('cpu'), _many_patches(torch.device('cpu')), spp=2, mb=1)
+    img, grads = _run(backend, device, _many_patches(device), spp=2, mb=1)
     ref_img, ref_grads = _run(oracle_util.load_oracle(), torch.device('cpu'), _many_patches(torch.device('cpu')), spp=2, mb=1)
     assert np.array_equal(img, ref_img)
     seen = 0
@@ -310,6 +310,16 @@ def test_gradient_store_spills_into_the_large_tier_hostsim(hostsim_backend):
         seen += n > 0
         assert np.linalg.norm(g - r) <= 1e-4 * n + 1e-12
     assert seen >= 10            # patches of both tiers received gradients
+
+
+def test_gradient_store_spills_into_the_large_tier_hostsim(hostsim_backend):
+    _spills_into_the_large_tier(hostsim_backend, torch.device('cpu'))
+
+
+@pytest.mark.gpu
+def test_gradient_store_spills_into_the_large_tier_gpu(gpu_backend):
+    """Where the address decides the tier for real (exec.h: replica_of); oracle/_ref travels to the GPU box with the snapshot."""
+    _spills_into_the_large_tier(gpu_backend, torch.device('cuda:0'))
 
 
 def _nonfinite_through_data(backend, device):
