@@ -447,6 +447,42 @@ int rdr_debug_grad_scatter(const rdr_scene *scene, const rdr_dscene_desc *d_scen
                            int num_lanes, const uint8_t *active, const int32_t *target, const int32_t *index,
                            const double *values);
 
+/* Test hooks: the three integer primitives that decide order, each alone (tests/test_exec_primitives.py).  All arrays are HOST
+ * memory; the hook allocates from the library's pool, uploads, launches on the calling thread's stream and downloads.  Every
+ * argument is checked on the host first: a bad one returns 1 (rdr_last_error names the hook) before anything is launched.
+ *
+ * rdr_debug_compact: one stable stream compaction (exec::compact_dev, or exec::compact when host_form = 1) of the list
+ *   in[0 .. min(count, upper)) -- in = NULL: the identity 0, 1, ... -- under the predicate keep[value] != 0.
+ *   upper          bound of the input count (0 .. 2^24)
+ *   count          < 0: the count is the host-only Count(upper); else a device int holding this value (above `upper`: it clamps)
+ *   in             `upper` values, each in [0, keep_len); NULL needs keep_len >= upper
+ *   append_upper   < 0: the kept items go to out[0 ...]; else they continue a list of `append_count` items (0 <= append_count
+ *                  <= append_upper, the count on the device, append_upper its bound)
+ *   dyn_inc        != 0: compact_dev is handed a device counter, which starts at result[2] and advances by dyn_inc when the
+ *                  input list is not empty
+ *   scratch        0 or 1: which compaction scratch of the calling thread
+ *   host_form      1: exec::compact, which reads the count back; only with count < 0, no append, dyn_inc = 0, no pos_out, scratch 0
+ *   out            max(append_upper, 0) + upper ints, uploaded before the call and downloaded after it: the caller sees every slot
+ *   pos_out        NULL, or as `out`: pos_out[k] = position in the input list of the k-th kept item
+ *   result[4]      [0] the count after the call, as the device holds it   [1] the bound of the returned Count
+ *                  [2] in: the dyn counter's start, out: its value after the call   [3] what the host form returned, or -1
+ *
+ * rdr_debug_walk: `repeat` launches back to back (no host synchronisation between them) of a walk over min(count, upper) items
+ *   through kind 0 exec::launch_persistent, 1 exec::launch_chunked(items_per_lane, idle_min, steps), 2 exec::launch (begin, all
+ *   steps and finish in one lane).  Item i walks len[i] steps (0 .. 65536; 0: begin returns false): begin adds 1 to begun[i],
+ *   step k = 1, 2, ... adds i * 31 + k to a 32-bit sum, finish adds 1 to finished[i] and stores the number of steps in
+ *   steps_taken[i] and the sum in acc[i] = (len * i * 31 + len * (len + 1) / 2) mod 2^32.  The four output arrays (`upper` entries)
+ *   are uploaded first, like `out` above.  items_per_lane 1 .. 64, idle_min 1 .. 64, steps 1 .. 1024 (what rdr_tuning clamps to);
+ *   gate_closed 0 or 1 (kind 0 only: the walker's gate_closed() reads a device flag of this value); repeat 1 .. 65536;
+ *   upper 0 .. 2^24; count as above.
+ *
+ * rdr_debug_sort_pairs: the stable 64-bit radix sort of the edge hierarchies' builder on n (1 .. 2^24) pairs. */
+int rdr_debug_compact(int upper, int count, const int32_t *in, const uint8_t *keep, int keep_len, int append_upper, int append_count,
+                      int dyn_inc, int scratch, int host_form, int32_t *out, int32_t *pos_out, int32_t *result /* [4] */);
+int rdr_debug_walk(int kind, int upper, int count, const int32_t *len, int items_per_lane, int idle_min, int steps, int gate_closed,
+                   int repeat, int32_t *begun, int32_t *finished, int32_t *steps_taken, uint32_t *acc);
+int rdr_debug_sort_pairs(const uint64_t *keys, const int32_t *vals, int n, uint64_t *keys_out, int32_t *vals_out);
+
 #ifdef __cplusplus
 }
 #endif

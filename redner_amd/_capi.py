@@ -154,7 +154,7 @@ EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_textu
            'rdr_mip_pyramid_backward',
            'rdr_mesh_topology_create', 'rdr_mesh_topology_destroy', 'rdr_mesh_topology_read', 'rdr_vertex_normal_scratch',
            'rdr_vertex_normal', 'rdr_vertex_normal_backward', 'rdr_debug_trace_plan', 'rdr_debug_scene_trace_plan',
-           'rdr_debug_grad_scatter')
+           'rdr_debug_grad_scatter', 'rdr_debug_compact', 'rdr_debug_walk', 'rdr_debug_sort_pairs')
 
 # rdr_scatter_op / rdr_scatter_target (rdr_debug_grad_scatter)
 SCATTER_ACCUM, SCATTER_ACCUM_TEXEL, SCATTER_ACCUM_PLAIN, SCATTER_ACCUM_TRIPLE, SCATTER_ACCUM_TEXEL_TRIPLE, \
@@ -255,6 +255,12 @@ def load(path=None):
     lib.rdr_debug_grad_scatter.restype = C.c_int
     lib.rdr_debug_grad_scatter.argtypes = [C.c_void_p, C.POINTER(DSceneDesc), C.c_uint64, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rdr_debug_compact.restype = C.c_int
+    lib.rdr_debug_compact.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3
+    lib.rdr_debug_walk.restype = C.c_int
+    lib.rdr_debug_walk.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4
+    lib.rdr_debug_sort_pairs.restype = C.c_int
+    lib.rdr_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     _lib, _lib_path = lib, path
     return lib
 

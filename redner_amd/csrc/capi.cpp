@@ -51,6 +51,59 @@ struct LibmProbe {
     }
 };
 
+// rdr_debug_compact: the predicate is a table look-up of the item's value
+struct KeepProbe {
+    const uint8_t *keep;
+    RDR_FN bool operator()(int v) const { return keep[v] != 0; }
+};
+// rdr_debug_walk: item i walks len[i] steps and leaves behind how often it was begun and finished, how many steps it took and a
+// sum that depends on the item and on every step number -- a lane that resumes with another lane's state shows in `acc`
+struct WalkProbe {
+    const int *len, *gate;
+    int *begun, *finished, *steps_taken; unsigned *acc;
+    struct State { int idx, left; unsigned k, acc; };
+    RDR_FN bool gate_closed() const { return *gate != 0; }
+    RDR_FN bool begin(int item, State &st) const {
+        rdr::atomic_fetch_add(&begun[item], 1);
+        st.idx = item; st.left = len[item]; st.k = 0; st.acc = 0;
+        return st.left > 0;
+    }
+    RDR_FN bool step(State &st) const {
+        st.acc += (unsigned)st.idx * 31u + ++st.k;
+        return --st.left == 0;
+    }
+    RDR_FN void finish(State &st) const {
+        rdr::atomic_fetch_add(&finished[st.idx], 1);
+        steps_taken[st.idx] = (int)st.k; acc[st.idx] = st.acc;
+    }
+};
+struct WalkProbeLane {             // the same walk as one lane of a plain launch
+    WalkProbe w;
+    RDR_FN void operator()(int i) const {
+        WalkProbe::State st;
+        if (w.begin(i, st)) { while (!w.step(st)) {} }
+        w.finish(st);
+    }
+};
+namespace {
+struct DebugHeld {                 // pool blocks of a test hook: released on every path out, also when a launch or a copy throws
+    std::vector<void *> p;
+    void *get(size_t bytes) { p.push_back(nullptr); p.back() = exec::pool_alloc(bytes ? bytes : 16); return p.back(); }
+    template <class T> T *put(const T *host, size_t n) { T *d = (T *)get(sizeof(T) * n); exec::upload(d, host, sizeof(T) * n); return d; }
+    ~DebugHeld() { exec::device_sync(); for (void *q : p) exec::pool_free(q); }
+};
+constexpr int kDebugMaxItems = 1 << 24;
+}
+#ifdef RDR_HOSTSIM
+// The CPU debugging harness defines the sort hook's body beside its other stand-ins for edges_gpu.cpp (tests/hostsim/
+// edges_gpu_stub.cpp); a harness directory that predates the hook still links and loads, and the hook says what is missing.
+namespace rdr {
+__attribute__((weak)) void debug_sort_pairs(const uint64_t *, const int32_t *, int, uint64_t *, int32_t *) {
+    throw std::runtime_error("rdr_debug_sort_pairs: this harness build has no stand-in for the sort");
+}
+}
+#endif
+
 extern "C" {
 
 const char *rdr_last_error(void) { return g_last_error.c_str(); }
@@ -500,6 +553,125 @@ int rdr_debug_grad_scatter(const rdr_scene *scene, const rdr_dscene_desc *d_scen
         exec::select_device(1, s.gpu_index);
         use_caller_stream();
         rdr::debug_grad_scatter(s, *d_scene, (size_t)job_samples, op, plain != 0, num_lanes, active, target, index, values);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+/* Test hook: one stream compaction as render.cpp calls it (count on the host or on the device, appended, with positions, with the
+ * edge sampler's counter, on the second scratch) or the host-visible form. */
+int rdr_debug_compact(int upper, int count, const int32_t *in, const uint8_t *keep, int keep_len, int append_upper, int append_count,
+                      int dyn_inc, int scratch, int host_form, int32_t *out, int32_t *pos_out, int32_t *result) {
+    try {
+        g_last_error.clear();
+        const auto bad = [](const std::string &what) { throw std::runtime_error("rdr_debug_compact: " + what); };
+        if (upper < 0 || upper > kDebugMaxItems) bad("upper out of range");
+        if (!keep || keep_len < 0 || keep_len > kDebugMaxItems || !out || !result) bad("keep, out and result are required");
+        if (count > kDebugMaxItems + 64) bad("count out of range");
+        if (in) {
+            for (int i = 0; i < upper; ++i) if (in[i] < 0 || in[i] >= keep_len) bad("value outside the keep table (item " + std::to_string(i) + ")");
+        } else if (keep_len < upper) bad("the keep table is shorter than the identity list");
+        const bool append = append_upper >= 0;
+        if (append_upper > kDebugMaxItems) bad("append_upper out of range");
+        if (append && (append_count < 0 || append_count > append_upper)) bad("append_count outside [0, append_upper]");
+        if (scratch != 0 && scratch != 1) bad("scratch must be 0 or 1");
+        if (host_form != 0 && host_form != 1) bad("host_form must be 0 or 1");
+        if (host_form && (count >= 0 || append || dyn_inc != 0 || pos_out || scratch != 0))
+            bad("the host form takes a host count, no append, no dyn, no pos_out, scratch 0");
+        std::lock_guard<std::recursive_mutex> lk(device_lock(exec::current_device()));
+        exec::select_device(1, exec::current_device());        // the calling thread's device: checked, not changed
+        use_caller_stream();
+        DebugHeld held;
+        const size_t out_len = (size_t)(append ? append_upper : 0) + (size_t)upper;
+        const int *d_in = in ? held.put(in, (size_t)upper) : nullptr;
+        const uint8_t *d_keep = held.put(keep, (size_t)keep_len);
+        int *d_out = held.put(out, out_len);
+        int *d_pos = pos_out ? held.put(pos_out, out_len) : nullptr;
+        const int *d_count = count >= 0 ? held.put(&count, 1) : nullptr;
+        const int *d_append = append ? held.put(&append_count, 1) : nullptr;
+        int *d_dyn = dyn_inc != 0 ? held.put(&result[2], 1) : nullptr;
+        const exec::Count n = d_count ? exec::Count(d_count, upper) : exec::Count(upper);
+        const exec::Count at(d_append, append ? append_upper : 0);
+        const KeepProbe pred{d_keep};
+        int32_t r[4] = {0, 0, result[2], -1};
+        if (host_form) {
+            r[3] = exec::compact(d_in, upper, d_out, pred);
+            r[0] = r[3]; r[1] = upper;
+        } else {
+            const exec::Count got = exec::compact_dev(d_in, n, d_out, pred, append ? &at : nullptr, d_dyn, dyn_inc, d_pos, scratch);
+            r[1] = got.upper;
+            if (got.dev) exec::download(&r[0], got.dev, sizeof(int)); else r[0] = got.upper;
+        }
+        if (d_dyn) exec::download(&r[2], d_dyn, sizeof(int));
+        exec::download(out, d_out, sizeof(int) * out_len);
+        if (d_pos) exec::download(pos_out, d_pos, sizeof(int) * out_len);
+        exec::sync();
+        std::memcpy(result, r, sizeof(r));
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+/* Test hook: the walk kernels with lane refill (and the plain launch) over a walker whose every begin, step and finish is counted. */
+int rdr_debug_walk(int kind, int upper, int count, const int32_t *len, int items_per_lane, int idle_min, int steps, int gate_closed,
+                   int repeat, int32_t *begun, int32_t *finished, int32_t *steps_taken, uint32_t *acc) {
+    try {
+        g_last_error.clear();
+        const auto bad = [](const std::string &what) { throw std::runtime_error("rdr_debug_walk: " + what); };
+        if (kind < 0 || kind > 2) bad("unknown kind");
+        if (upper < 0 || upper > kDebugMaxItems) bad("upper out of range");
+        if (count > kDebugMaxItems + 64) bad("count out of range");
+        if (!len || !begun || !finished || !steps_taken || !acc) bad("a per-item array is missing");
+        for (int i = 0; i < upper; ++i) if (len[i] < 0 || len[i] > 65536) bad("walk length outside [0, 65536] (item " + std::to_string(i) + ")");
+        // what resolve_tuning (tuning.h) clamps to; items_per_lane = 0 would hand out empty chunks for ever
+        if (items_per_lane < 1 || items_per_lane > 64) bad("items_per_lane outside [1, 64]");
+        if (idle_min < 1 || idle_min > 64) bad("idle_min outside [1, 64]");
+        if (steps < 1 || steps > 1024) bad("steps outside [1, 1024]");
+        if (gate_closed != 0 && (gate_closed != 1 || kind != 0)) bad("gate_closed is 0, or 1 with kind 0");
+        if (repeat < 1 || repeat > 65536) bad("repeat outside [1, 65536]");
+        std::lock_guard<std::recursive_mutex> lk(device_lock(exec::current_device()));
+        exec::select_device(1, exec::current_device());        // the calling thread's device: checked, not changed
+        use_caller_stream();
+        DebugHeld held;
+        const size_t n = (size_t)upper;
+        WalkProbe w;
+        w.len = held.put(len, n);
+        w.gate = held.put(&gate_closed, 1);
+        w.begun = held.put(begun, n); w.finished = held.put(finished, n); w.steps_taken = held.put(steps_taken, n);
+        w.acc = held.put(acc, n);
+        const int *d_count = count >= 0 ? held.put(&count, 1) : nullptr;
+        const exec::Count c = d_count ? exec::Count(d_count, upper) : exec::Count(upper);
+        for (int r = 0; r < repeat; ++r) {
+            if (kind == 0) exec::launch_persistent(c, w);
+            else if (kind == 1) exec::launch_chunked(c, w, items_per_lane, idle_min, steps);
+            else exec::launch(c, WalkProbeLane{w});
+        }
+        exec::download(begun, w.begun, sizeof(int) * n);
+        exec::download(finished, w.finished, sizeof(int) * n);
+        exec::download(steps_taken, w.steps_taken, sizeof(int) * n);
+        exec::download(acc, w.acc, sizeof(unsigned) * n);
+        exec::sync();
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+/* Test hook: the stable radix sort of (64-bit code, edge id) pairs (edges_gpu.cpp: debug_sort_pairs). */
+int rdr_debug_sort_pairs(const uint64_t *keys, const int32_t *vals, int n, uint64_t *keys_out, int32_t *vals_out) {
+    try {
+        g_last_error.clear();
+        if (n < 1 || n > kDebugMaxItems) throw std::runtime_error("rdr_debug_sort_pairs: n outside [1, 2^24]");
+        if (!keys || !vals || !keys_out || !vals_out) throw std::runtime_error("rdr_debug_sort_pairs: an array is missing");
+        std::lock_guard<std::recursive_mutex> lk(device_lock(exec::current_device()));
+        exec::select_device(1, exec::current_device());        // the calling thread's device: checked, not changed
+        use_caller_stream();
+        rdr::debug_sort_pairs(keys, vals, n, keys_out, vals_out);
         return 0;
     } catch (const std::exception &e) {
         set_error(e.what());

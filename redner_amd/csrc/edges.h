@@ -282,5 +282,8 @@ void drop_gather_cache();                        // the billboard hierarchy kept
 void gather_hierarchy_device(EdgeData &ed);      // edges_gpu.cpp: EdgeSceneD::gather from ed.gather_boxes (build or refit, by kernels)
 void download_edge_trees(EdgeData &ed);
 void delete_edge_data(EdgeData *e);
+// rdr_debug_sort_pairs (include/redner_amd.h): the builder's stable sort of (64-bit code, edge id) pairs on its own; HOST arrays,
+// n >= 1.  edges_gpu.cpp: the radix_* kernels on the calling thread's stream; the CPU debugging harness: std::stable_sort.
+void debug_sort_pairs(const uint64_t *keys, const int32_t *vals, int n, uint64_t *keys_out, int32_t *vals_out);
 
 } // namespace rdr

@@ -866,4 +866,25 @@ void download_edge_trees(EdgeData &ed) {
     }
 }
 
+// rdr_debug_sort_pairs: the sort above on its own, with the scratch the builder gives it
+void debug_sort_pairs(const uint64_t *keys, const int32_t *vals, int n, uint64_t *keys_out, int32_t *vals_out) {
+    if (n < 1 || !keys || !vals || !keys_out || !vals_out) throw std::runtime_error("rdr_debug_sort_pairs: bad arguments");
+    hipStream_t s = exec::ctx().stream;
+    struct Temporaries {
+        hipStream_t s; std::vector<void *> blocks;
+        ~Temporaries() { (void)hipStreamSynchronize(s); for (void *p : blocks) exec::pool_free(p); }
+    } temporaries{s, {}};
+    auto talloc = [&](size_t bytes) -> void * { void *p = exec::pool_alloc(bytes); temporaries.blocks.push_back(p); return p; };
+    const size_t kbytes = sizeof(uint64_t) * (size_t)n, vbytes = sizeof(int) * (size_t)n;
+    uint64_t *k_in = (uint64_t *)talloc(kbytes), *k_tmp = (uint64_t *)talloc(kbytes), *k_out = (uint64_t *)talloc(kbytes);
+    int *v_in = (int *)talloc(vbytes), *v_tmp = (int *)talloc(vbytes), *v_out = (int *)talloc(vbytes);
+    int *hist = (int *)talloc(sizeof(int) * 256 * (size_t)((n + kSortTile - 1) / kSortTile));
+    exec::upload(k_in, keys, kbytes);
+    exec::upload(v_in, vals, vbytes);
+    radix_sort_pairs_u64(s, k_tmp, v_tmp, k_in, v_in, k_out, v_out, n, hist);
+    exec::check(hipGetLastError(), "radix sort launch");
+    exec::download(keys_out, k_out, kbytes);
+    exec::download(vals_out, v_out, vbytes);
+}
+
 }  // namespace rdr

@@ -120,7 +120,7 @@ template <class F>
 inline void launch(Count c, const F &f) { const int n = c.value(); note_launch(typeid(F).name(), n); for (int i = 0; i < n; ++i) f(i); }
 inline int *persistent_counter() { static int ring[64]; static int at = 0; at = (at + 1) % 64; ring[at] = 0; return ring + at; }
 template <class W>
-inline void launch_persistent(Count c, const W &w) {          // see hip/exec.h: begin / step... / finish per item
+inline void walk_items(Count c, const W &w) {                 // see hip/exec.h: begin / step... / finish per item
     const int n = c.value();
     note_launch(typeid(W).name(), n);
     for (int i = 0; i < n; ++i) {
@@ -129,8 +129,16 @@ inline void launch_persistent(Count c, const W &w) {          // see hip/exec.h:
         w.finish(st);
     }
 }
+// as hip/exec.h: a walker may have `bool gate_closed() const`; launch_persistent then touches no item, launch_chunked never asks
+template <class W, class = void> struct WalkGate { static bool closed(const W &) { return false; } };
+template <class W> struct WalkGate<W, decltype((void)&W::gate_closed)> { static bool closed(const W &w) { return w.gate_closed(); } };
 template <class W>
-inline void launch_chunked(Count c, const W &w, int = 4, int = 16, int = 8) { launch_persistent(c, w); }     // (hip/exec.h: wave-local refill)
+inline void launch_persistent(Count c, const W &w) {
+    if (c.upper <= 0 || WalkGate<W>::closed(w)) return;
+    walk_items(c, w);
+}
+template <class W>
+inline void launch_chunked(Count c, const W &w, int = 4, int = 16, int = 8) { walk_items(c, w); }     // (hip/exec.h: wave-local refill)
 } // namespace exec
 
 // ---- host stand-ins for the hand-written kernels (compact.hip / trace.hip) ----------------------
