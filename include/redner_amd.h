@@ -303,6 +303,36 @@ int rdr_mip_pyramid(int height, int width, int channels, int num_levels, float *
 int rdr_mip_pyramid_backward(int height, int width, int channels, int num_levels, const float *const *d_levels, float *d_texels,
                              float *scratch, int64_t scratch_floats, int gpu_index);
 
+/* An environment map from spherical-harmonic coefficients (pyredner/utils.py:10-60, SH_reconstruct), its adjoint, and the sampling
+ * tables of an environment map (pyredner/envmap.py:36-60, generate_envmap_pdf); csrc/sh_envmap.h pins the meaning, the fp32
+ * arithmetic and the summation orders.
+ *   rdr_sh_reconstruct           image [height, width, channels] = max(sum_i Y_i(theta_r, phi_c) coeffs[ch, i], 0) from coeffs
+ *                                [channels, num_coeffs] (contiguous); int(sqrt(num_coeffs)) bands, at most 8; the columns past
+ *                                bands^2 are not read.  `clamp` [height, width, channels] bytes (may be NULL) receives twice the
+ *                                derivative of the clamp: 2 where the sum is > 0, 0 where it is < 0, 1 at a tie.  One launch.
+ *   rdr_sh_reconstruct_backward  d_coeffs [channels, num_coeffs], every element, from d_image and the forward call's `clamp`: a
+ *                                reduction in a fixed order (fp64 partial sums per 32 x 32 tile in row-major order, the tiles in
+ *                                ascending order, one rounding to fp32), no float atomics; the columns past bands^2 get 0.
+ *                                `scratch`: at least rdr_sh_backward_scratch(...) floats, aligned to 8 bytes, in the same memory as
+ *                                the tensors; its contents afterwards are unspecified.  Two launches.
+ *   rdr_envmap_tables            sample_cdf_ys [height] and sample_cdf_xs [height, width] from texels [height, width, 3] and
+ *                                y_weight [height] (the caller's sin(pi (y + 0.5) / height)), with the running sums taken as
+ *                                torch.cumsum takes them on the CPU: a sequential fp64 accumulator rounded to fp32 at every output.
+ *                                `*total` (HOST memory) receives the last unnormalised entry of the column table (pdf_norm is
+ *                                height * width / (*total * 2 pi^2)).  Two launches and ONE synchronisation (that read-back).
+ * The calls fail (rdr_last_error) for a size that is not positive, a side above 32768, an image above 2^30 floats, more than 8
+ * bands, or a required pointer that is NULL.  Pointers are DEVICE memory of gpu_index; a negative gpu_index means host memory and is
+ * accepted by the CPU debugging harness only.  Launches are ordered on the rdr_set_stream stream; the two SH calls are NOT
+ * synchronised.  Results are bitwise reproducible from run to run, and the harness computes the same bits as the kernels.
+ * Return 0 on success. */
+int64_t rdr_sh_backward_scratch(int height, int width, int channels, int num_coeffs);     /* floats; -1 on error */
+int rdr_sh_reconstruct(const float *coeffs, int channels, int num_coeffs, int height, int width, float *image, uint8_t *clamp,
+                       int gpu_index);
+int rdr_sh_reconstruct_backward(const uint8_t *clamp, const float *d_image, int channels, int num_coeffs, int height, int width,
+                                float *d_coeffs, float *scratch, int64_t scratch_floats, int gpu_index);
+int rdr_envmap_tables(const float *texels, const float *y_weight, int height, int width, float *sample_cdf_ys, float *sample_cdf_xs,
+                      float *total, int gpu_index);
+
 /* Smooth vertex normals of a triangle mesh (pyredner/shape.py:7-127, compute_vertex_normal) and their vertex adjoint
  * (csrc/vertex_normal.h, which pins the meaning, the arithmetic and the summation order).  vertices [V, 3] fp32, indices [T, 3]
  * int32, normals [V, 3] fp32.

@@ -6,7 +6,10 @@
                                  render_pathtracing / render_generic; all exported here:
                                  `from redner_amd import render_deferred, PointLight`
     redner_amd.texture           mip-mapped Texture / EnvironmentMap and generate_mipmap on the native pyramid kernels:
-                                 `from redner_amd import Texture, EnvironmentMap, generate_mipmap`
+                                 `from redner_amd import Texture, EnvironmentMap, generate_mipmap`; envmap_sampling_tables:
+                                 the sampling tables of an environment map by one native call
+    redner_amd.utils             SH_reconstruct on the native spherical-harmonic kernels (a coefficient gradient included):
+                                 `from redner_amd import SH_reconstruct`
     redner_amd.shape             compute_vertex_normal on the native vertex-normal kernels (a vertex gradient included):
                                  `from redner_amd import compute_vertex_normal, MeshTopology`
     redner_amd.install()         register redner_amd.redner as `redner` for the reference's
@@ -16,7 +19,8 @@ import sys
 
 _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'DeferredShade',
                  'deferred_shade', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo', 'render_pathtracing')
-_TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid')
+_TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid', 'envmap_sampling_tables')
+_UTILS = ('SH_reconstruct', 'SHReconstruct')
 _SHAPE = ('compute_vertex_normal', 'MeshTopology', 'VertexNormals')
 
 
@@ -31,6 +35,9 @@ def __getattr__(name):
     if name in _SHAPE:
         from . import shape
         return getattr(shape, name)
+    if name in _UTILS:
+        from . import utils
+        return getattr(utils, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 

@@ -152,6 +152,7 @@ EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_textu
            'rdr_deferred_shade', 'rdr_deferred_shade_backward',
            'rdr_mip_num_levels', 'rdr_mip_backward_scratch', 'rdr_mip_tiled_stages', 'rdr_mip_pyramid',
            'rdr_mip_pyramid_backward',
+           'rdr_sh_backward_scratch', 'rdr_sh_reconstruct', 'rdr_sh_reconstruct_backward', 'rdr_envmap_tables',
            'rdr_mesh_topology_create', 'rdr_mesh_topology_destroy', 'rdr_mesh_topology_read', 'rdr_vertex_normal_scratch',
            'rdr_vertex_normal', 'rdr_vertex_normal_backward', 'rdr_debug_trace_plan', 'rdr_debug_scene_trace_plan',
            'rdr_debug_grad_scatter', 'rdr_debug_compact', 'rdr_debug_walk', 'rdr_debug_sort_pairs')
@@ -235,6 +236,14 @@ def load(path=None):
     lib.rdr_mip_pyramid_backward.restype = C.c_int
     lib.rdr_mip_pyramid_backward.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                              C.c_int64, C.c_int]
+    lib.rdr_sh_backward_scratch.restype = C.c_int64
+    lib.rdr_sh_backward_scratch.argtypes = [C.c_int] * 4
+    lib.rdr_sh_reconstruct.restype = C.c_int
+    lib.rdr_sh_reconstruct.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int]
+    lib.rdr_sh_reconstruct_backward.restype = C.c_int
+    lib.rdr_sh_reconstruct_backward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+    lib.rdr_envmap_tables.restype = C.c_int
+    lib.rdr_envmap_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int]
     lib.rdr_mesh_topology_create.restype = C.c_void_p
     lib.rdr_mesh_topology_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.rdr_mesh_topology_destroy.restype = None

@@ -7,6 +7,7 @@
 #include "deferred.h"
 #include "mipmap.h"
 #include "vertex_normal.h"
+#include "sh_envmap.h"
 #include <cstdio>
 #include "scene.h"
 #include <cstring>
@@ -242,6 +243,60 @@ int rdr_mip_pyramid_backward(int height, int width, int channels, int num_levels
         mip_select(gpu_index, "rdr_mip_pyramid_backward");
         rdr::mip::pyramid_backward(height, width, channels, num_levels, d_levels, d_texels, scratch,
                                    scratch_floats > 0 ? (size_t)scratch_floats : 0);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+// ---- SH reconstruction and the sampling tables of an environment map (csrc/sh_envmap.h) ----
+int64_t rdr_sh_backward_scratch(int height, int width, int channels, int num_coeffs) {
+    try {
+        g_last_error.clear();
+        return (int64_t)rdr::shenv::scratch_floats(rdr::shenv::make_plan(height, width, channels, num_coeffs, "rdr_sh_backward_scratch"));
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return -1;
+    }
+}
+
+int rdr_sh_reconstruct(const float *coeffs, int channels, int num_coeffs, int height, int width, float *image, uint8_t *clamp,
+                       int gpu_index) {
+    try {
+        g_last_error.clear();
+        std::lock_guard<std::recursive_mutex> lk(device_lock(gpu_index));
+        mip_select(gpu_index, "rdr_sh_reconstruct");
+        rdr::shenv::reconstruct(height, width, channels, num_coeffs, coeffs, image, clamp);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_sh_reconstruct_backward(const uint8_t *clamp, const float *d_image, int channels, int num_coeffs, int height, int width,
+                                float *d_coeffs, float *scratch, int64_t scratch_floats, int gpu_index) {
+    try {
+        g_last_error.clear();
+        std::lock_guard<std::recursive_mutex> lk(device_lock(gpu_index));
+        mip_select(gpu_index, "rdr_sh_reconstruct_backward");
+        rdr::shenv::reconstruct_backward(height, width, channels, num_coeffs, clamp, d_image, d_coeffs, scratch,
+                                         scratch_floats > 0 ? (size_t)scratch_floats : 0);
+        return 0;
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return 1;
+    }
+}
+
+int rdr_envmap_tables(const float *texels, const float *y_weight, int height, int width, float *sample_cdf_ys, float *sample_cdf_xs,
+                      float *total, int gpu_index) {
+    try {
+        g_last_error.clear();
+        std::lock_guard<std::recursive_mutex> lk(device_lock(gpu_index));
+        mip_select(gpu_index, "rdr_envmap_tables");
+        rdr::shenv::tables(height, width, texels, y_weight, sample_cdf_ys, sample_cdf_xs, total);
         return 0;
     } catch (const std::exception &e) {
         set_error(e.what());

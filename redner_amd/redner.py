@@ -501,6 +501,48 @@ def mip_pyramid_backward(d_levels, d_texels, scratch, scratch_floats, height, wi
         raise RuntimeError('redner.mip_pyramid_backward: ' + _capi.last_error())
 
 
+def sh_backward_scratch(height, width, channels, num_coeffs):
+    """Not in the reference's module: floats of scratch sh_reconstruct_backward needs (rdr_sh_backward_scratch)."""
+    n = int(_capi.lib().rdr_sh_backward_scratch(int(height), int(width), int(channels), int(num_coeffs)))
+    if n < 0:
+        raise RuntimeError('redner.sh_backward_scratch: ' + _capi.last_error())
+    return n
+
+
+def sh_reconstruct(coeffs, image, clamp, channels, num_coeffs, height, width, use_gpu, gpu_index):
+    """Not in the reference's module (its SH_reconstruct is torch code, pyredner/utils.py): rdr_sh_reconstruct
+    (include/redner_amd.h).  coeffs: float_ptr of [channels, num_coeffs]; writes image [height, width, channels] and, unless it
+    is None, the clamp bytes.  Ordered on the current torch stream, not synchronised."""
+    lib = _capi.lib()
+    _use_torch_stream(lib, use_gpu, gpu_index)
+    if lib.rdr_sh_reconstruct(_addr(coeffs) or None, int(channels), int(num_coeffs), int(height), int(width), _addr(image) or None,
+                              _addr(clamp) or None, int(gpu_index) if use_gpu else -1) != 0:
+        raise RuntimeError('redner.sh_reconstruct: ' + _capi.last_error())
+
+
+def sh_reconstruct_backward(clamp, d_image, d_coeffs, scratch, scratch_floats, channels, num_coeffs, height, width, use_gpu,
+                            gpu_index):
+    """Not in the reference's module: rdr_sh_reconstruct_backward.  Writes every element of d_coeffs [channels, num_coeffs]."""
+    lib = _capi.lib()
+    _use_torch_stream(lib, use_gpu, gpu_index)
+    if lib.rdr_sh_reconstruct_backward(_addr(clamp) or None, _addr(d_image) or None, int(channels), int(num_coeffs), int(height),
+                                       int(width), _addr(d_coeffs) or None, _addr(scratch) or None, int(scratch_floats),
+                                       int(gpu_index) if use_gpu else -1) != 0:
+        raise RuntimeError('redner.sh_reconstruct_backward: ' + _capi.last_error())
+
+
+def envmap_tables(texels, y_weight, sample_cdf_ys, sample_cdf_xs, height, width, use_gpu, gpu_index):
+    """Not in the reference's module (its tables are torch code, pyredner/envmap.py): rdr_envmap_tables.  float_ptr arguments;
+    writes both tables and returns the last unnormalised entry of the column table (one synchronisation)."""
+    lib = _capi.lib()
+    _use_torch_stream(lib, use_gpu, gpu_index)
+    total = C.c_float(0.0)
+    if lib.rdr_envmap_tables(_addr(texels) or None, _addr(y_weight) or None, int(height), int(width), _addr(sample_cdf_ys) or None,
+                             _addr(sample_cdf_xs) or None, C.byref(total), int(gpu_index) if use_gpu else -1) != 0:
+        raise RuntimeError('redner.envmap_tables: ' + _capi.last_error())
+    return float(total.value)
+
+
 class NormalWeighting(enum.IntEnum):
     """Not in the reference's module: rdr_normal_weighting, the weighting_scheme strings of pyredner.compute_vertex_normal."""
     max = 0

@@ -27,6 +27,8 @@ debugging harness only (the test-suite loads it); the product library raises for
 `render_pytorch.Texture` / `render_pytorch.EnvironmentMap` keep their one-level behaviour; the classes here derive from them
 and are accepted wherever those are (Material, Scene, RenderFunction.serialize_scene).
 """
+import math
+
 import torch
 
 from . import redner as _default_backend
@@ -147,18 +149,64 @@ class Texture(render_pytorch.Texture):
         return out
 
 
+_y_weights = {}                 # (H, device) -> sin(pi (y + 0.5) / H), the weights of the rows of a latitude-longitude map, on that device
+
+
+def _y_weight(height, device):
+    key = (height, str(device))
+    if key not in _y_weights:
+        # the very expression of render_pytorch.EnvironmentMap.generate_envmap_pdf, evaluated ON THE CPU as the reference's tables
+        # are and copied to the texels' device once: the device's own sin differs from the CPU's in the last bit of some rows
+        # (seen at 16 rows on an MI355X), and with it sample_cdf_ys would not be the reference's table
+        _y_weights[key] = torch.sin(math.pi * (torch.arange(height, dtype=torch.float32, device='cpu') + 0.5)
+                                    / float(height)).contiguous().to(device)
+    return _y_weights[key]
+
+
+def envmap_sampling_tables(texels, backend=None):
+    """(sample_cdf_ys [H], sample_cdf_xs [H, W], pdf_norm) of an environment map with level 0 `texels` [H, W, 3] fp32
+    (pyredner/envmap.py:36-60), by one native call (rdr_envmap_tables, csrc/sh_envmap.h).  The running sums are taken as
+    torch.cumsum takes them on the CPU -- a sequential fp64 accumulator rounded to fp32 at every output -- also on the device,
+    where torch's scan associates differently: the tables of a map built on the device are the reference's.  For CPU tensors
+    (the CPU debugging harness) all three results are bit for bit those of render_pytorch.EnvironmentMap.generate_envmap_pdf."""
+    rd = backend or _default_backend
+    if not isinstance(texels, torch.Tensor) or texels.dim() != 3 or int(texels.shape[2]) != 3 or texels.numel() == 0:
+        raise RuntimeError('envmap_sampling_tables: texels must be an [H, W, 3] tensor with H, W >= 1, got %s'
+                           % (tuple(texels.shape) if isinstance(texels, torch.Tensor) else type(texels),))
+    if texels.dtype != torch.float32:
+        raise RuntimeError('envmap_sampling_tables: fp32 texels only')
+    base = texels.detach().contiguous()
+    h, w = int(base.shape[0]), int(base.shape[1])
+    use_gpu, index = _place(base)
+    y_weight = _y_weight(h, base.device)
+    cdf_ys = torch.empty(h, dtype=torch.float32, device=base.device)
+    cdf_xs = torch.empty(h, w, dtype=torch.float32, device=base.device)
+    try:
+        total = rd.envmap_tables(rd.float_ptr(base.data_ptr()), rd.float_ptr(y_weight.data_ptr()), rd.float_ptr(cdf_ys.data_ptr()),
+                                 rd.float_ptr(cdf_xs.data_ptr()), h, w, use_gpu, index)
+    except RuntimeError as e:
+        raise RuntimeError('envmap_sampling_tables: %s' % e) from e
+    pdf_norm = (h * w) / (total * (2 * math.pi * math.pi))
+    return cdf_ys, cdf_xs, pdf_norm
+
+
 class EnvironmentMap(render_pytorch.EnvironmentMap):
     """pyredner.EnvironmentMap: a tensor becomes a mip-mapped Texture; assigning `.values` rebuilds the sampling tables
-    (from level 0, by render_pytorch.EnvironmentMap.generate_envmap_pdf), assigning `.env_to_world` refreshes `world_to_env`."""
+    (from level 0, by envmap_sampling_tables: one native call), assigning `.env_to_world` refreshes `world_to_env`."""
 
     def __init__(self, values, env_to_world=None, directly_visible=True, backend=None):
         if isinstance(values, torch.Tensor):
             values = Texture(values, backend=backend)
         env_to_world = env_to_world if env_to_world is not None else torch.eye(4, 4)
         assert env_to_world.dtype == torch.float32
+        self._backend = backend
         self.directly_visible = directly_visible
         self.env_to_world = env_to_world
         self.values = values
+
+    def generate_envmap_pdf(self):
+        backend = getattr(self, '_backend', None) or getattr(self._values, '_backend', None)
+        self.sample_cdf_ys, self.sample_cdf_xs, self.pdf_norm = envmap_sampling_tables(self._values.mipmap[0], backend)
 
     @property
     def values(self):
