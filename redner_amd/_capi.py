@@ -144,18 +144,56 @@ class DeferredDesc(C.Structure):
 # rdr_deferred_light_type
 DL_AMBIENT, DL_POINT, DL_DIRECTIONAL, DL_SPOT = range(4)
 
-EXPORTS = ('rdr_scene_create', 'rdr_scene_destroy', 'rdr_scene_max_generic_texture_dimension',
-           'rdr_render', 'rdr_compute_num_channels', 'rdr_last_error',
-           'rdr_trace_stats_enable', 'rdr_trace_stats_reset', 'rdr_trace_stats_get', 'rdr_scene_trace',
-           'rdr_debug_counters_get', 'rdr_trim_cache', 'rdr_debug_dump_edges', 'rdr_debug_bvh_check',
-           'rdr_set_stream', 'rdr_set_pool_cap_mb', 'rdr_get_pool_cap_mb', 'rdr_set_build_flags', 'rdr_debug_libm', 'rdr_libm_exact',
-           'rdr_deferred_shade', 'rdr_deferred_shade_backward',
-           'rdr_mip_num_levels', 'rdr_mip_backward_scratch', 'rdr_mip_tiled_stages', 'rdr_mip_pyramid',
-           'rdr_mip_pyramid_backward',
-           'rdr_sh_backward_scratch', 'rdr_sh_reconstruct', 'rdr_sh_reconstruct_backward', 'rdr_envmap_tables',
-           'rdr_mesh_topology_create', 'rdr_mesh_topology_destroy', 'rdr_mesh_topology_read', 'rdr_vertex_normal_scratch',
-           'rdr_vertex_normal', 'rdr_vertex_normal_backward', 'rdr_debug_trace_plan', 'rdr_debug_scene_trace_plan',
-           'rdr_debug_grad_scatter', 'rdr_debug_compact', 'rdr_debug_walk', 'rdr_debug_sort_pairs')
+_p, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
+# Every symbol of include/redner_amd.h: name -> (restype, argtypes).  load() sets both on each function; a handle or pointer
+# without argtypes would go through ctypes' default int conversion (tests/test_capi.py compares this table with the header).
+SIGNATURES = {
+    'rdr_last_error': (C.c_char_p, []),
+    'rdr_scene_create': (_p, [C.POINTER(CameraDesc), C.POINTER(ShapeDesc), _i, C.POINTER(MaterialDesc), _i,
+                              C.POINTER(AreaLightDesc), _i, C.POINTER(EnvmapDesc), _i, _i, _i, _i]),
+    'rdr_scene_destroy': (None, [_p]),
+    'rdr_scene_max_generic_texture_dimension': (_i, [_p]),
+    'rdr_render': (_i, [_p, C.POINTER(RenderOptionsDesc), _p, _p, C.POINTER(DSceneDesc), _p, _p]),
+    'rdr_compute_num_channels': (_i, [C.POINTER(C.c_int), _i, _i]),
+    'rdr_trace_stats_enable': (None, [_i, _i]),
+    'rdr_trace_stats_reset': (None, []),
+    'rdr_trace_stats_get': (None, [C.POINTER(TraceStats)]),
+    'rdr_scene_trace': (_i, [_p, _p, _p, _i, _i]),
+    'rdr_trim_cache': (C.c_uint64, []),
+    'rdr_set_stream': (None, [_p]),
+    'rdr_set_pool_cap_mb': (None, [_i64]),
+    'rdr_get_pool_cap_mb': (_i64, []),
+    'rdr_set_build_flags': (None, [C.c_uint]),
+    'rdr_libm_exact': (_i, []),
+    'rdr_deferred_shade': (_i, [C.POINTER(DeferredDesc), _p, _p, _p]),
+    'rdr_deferred_shade_backward': (_i, [C.POINTER(DeferredDesc), _p, _p, _p, _p, _p]),
+    'rdr_mip_num_levels': (_i, [_i, _i]),
+    'rdr_mip_backward_scratch': (_i64, [_i, _i, _i]),
+    'rdr_mip_tiled_stages': (_i, [_i, _i, _i]),
+    'rdr_mip_pyramid': (_i, [_i, _i, _i, _i, C.POINTER(_p), _i]),
+    'rdr_mip_pyramid_backward': (_i, [_i, _i, _i, _i, C.POINTER(_p), _p, _p, _i64, _i]),
+    'rdr_sh_backward_scratch': (_i64, [_i] * 4),
+    'rdr_sh_reconstruct': (_i, [_p] + [_i] * 4 + [_p, _p, _i]),
+    'rdr_sh_reconstruct_backward': (_i, [_p, _p] + [_i] * 4 + [_p, _p, _i64, _i]),
+    'rdr_envmap_tables': (_i, [_p, _p, _i, _i, _p, _p, C.POINTER(C.c_float), _i]),
+    'rdr_mesh_topology_create': (_p, [_p, _i, _i, _i, _i]),
+    'rdr_mesh_topology_destroy': (None, [_p]),
+    'rdr_mesh_topology_read': (_i, [_p, _p, _p]),
+    'rdr_vertex_normal_scratch': (_i, [_p, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    'rdr_vertex_normal': (_i, [_p, _i, _p, _p, _p, _p, _i64]),
+    'rdr_vertex_normal_backward': (_i, [_p, _i, _p, _p, _p, _p, _p, _i64]),
+    'rdr_debug_counters_get': (None, [C.POINTER(DebugCounters)]),
+    'rdr_debug_dump_edges': (_i, [_p, C.c_char_p]),
+    'rdr_debug_bvh_check': (_i, [_p]),
+    'rdr_debug_libm': (_i, [_i, _p, _p, _p, _i]),
+    'rdr_debug_trace_plan': (_i, [_i] * 8 + [C.POINTER(Tuning), _p]),
+    'rdr_debug_scene_trace_plan': (_i, [_p] + [_i] * 4 + [C.POINTER(Tuning), _p]),
+    'rdr_debug_grad_scatter': (_i, [_p, C.POINTER(DSceneDesc), C.c_uint64, _i, _i, _i, _p, _p, _p, _p]),
+    'rdr_debug_compact': (_i, [_i, _i, _p, _p] + [_i] * 6 + [_p] * 3),
+    'rdr_debug_walk': (_i, [_i, _i, _i, _p] + [_i] * 5 + [_p] * 4),
+    'rdr_debug_sort_pairs': (_i, [_p, _p, _i, _p, _p]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 # rdr_scatter_op / rdr_scatter_target (rdr_debug_grad_scatter)
 SCATTER_ACCUM, SCATTER_ACCUM_TEXEL, SCATTER_ACCUM_PLAIN, SCATTER_ACCUM_TRIPLE, SCATTER_ACCUM_TEXEL_TRIPLE, \
@@ -181,95 +219,9 @@ def load(path=None):
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise RuntimeError("redner_amd: %s does not export %s" % (path, name))
-    lib.rdr_scene_create.restype = C.c_void_p
-    lib.rdr_scene_create.argtypes = [C.POINTER(CameraDesc), C.POINTER(ShapeDesc), C.c_int,
-                                     C.POINTER(MaterialDesc), C.c_int, C.POINTER(AreaLightDesc), C.c_int,
-                                     C.POINTER(EnvmapDesc), C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.rdr_scene_destroy.restype = None
-    lib.rdr_scene_destroy.argtypes = [C.c_void_p]
-    lib.rdr_scene_max_generic_texture_dimension.restype = C.c_int
-    lib.rdr_scene_max_generic_texture_dimension.argtypes = [C.c_void_p]
-    lib.rdr_render.restype = C.c_int
-    lib.rdr_render.argtypes = [C.c_void_p, C.POINTER(RenderOptionsDesc), C.c_void_p, C.c_void_p,
-                               C.POINTER(DSceneDesc), C.c_void_p, C.c_void_p]
-    lib.rdr_compute_num_channels.restype = C.c_int
-    lib.rdr_compute_num_channels.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int]
-    lib.rdr_last_error.restype = C.c_char_p
-    lib.rdr_last_error.argtypes = []
-    lib.rdr_trace_stats_enable.restype = None
-    lib.rdr_trace_stats_enable.argtypes = [C.c_int, C.c_int]
-    lib.rdr_trace_stats_reset.restype = None
-    lib.rdr_debug_counters_get.restype = None
-    lib.rdr_debug_counters_get.argtypes = [C.POINTER(DebugCounters)]
-    lib.rdr_trim_cache.restype = C.c_uint64
-    lib.rdr_trim_cache.argtypes = []
-    lib.rdr_debug_bvh_check.restype = C.c_int
-    lib.rdr_debug_bvh_check.argtypes = [C.c_void_p]
-    lib.rdr_set_stream.restype = None
-    lib.rdr_set_stream.argtypes = [C.c_void_p]
-    lib.rdr_set_pool_cap_mb.restype = None
-    lib.rdr_set_pool_cap_mb.argtypes = [C.c_int64]
-    lib.rdr_get_pool_cap_mb.restype = C.c_int64
-    lib.rdr_get_pool_cap_mb.argtypes = []
-    lib.rdr_set_build_flags.restype = None
-    lib.rdr_set_build_flags.argtypes = [C.c_uint]
-    lib.rdr_trace_stats_get.restype = None
-    lib.rdr_trace_stats_get.argtypes = [C.POINTER(TraceStats)]
-    lib.rdr_scene_trace.restype = C.c_int
-    lib.rdr_scene_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-    lib.rdr_libm_exact.restype = C.c_int
-    lib.rdr_libm_exact.argtypes = []
-    lib.rdr_debug_libm.restype = C.c_int
-    lib.rdr_debug_libm.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.rdr_deferred_shade.restype = C.c_int
-    lib.rdr_deferred_shade.argtypes = [C.POINTER(DeferredDesc), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rdr_deferred_shade_backward.restype = C.c_int
-    lib.rdr_deferred_shade_backward.argtypes = [C.POINTER(DeferredDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rdr_mip_num_levels.restype = C.c_int
-    lib.rdr_mip_num_levels.argtypes = [C.c_int, C.c_int]
-    lib.rdr_mip_backward_scratch.restype = C.c_int64
-    lib.rdr_mip_backward_scratch.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.rdr_mip_tiled_stages.restype = C.c_int
-    lib.rdr_mip_tiled_stages.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.rdr_mip_pyramid.restype = C.c_int
-    lib.rdr_mip_pyramid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int]
-    lib.rdr_mip_pyramid_backward.restype = C.c_int
-    lib.rdr_mip_pyramid_backward.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
-                                             C.c_int64, C.c_int]
-    lib.rdr_sh_backward_scratch.restype = C.c_int64
-    lib.rdr_sh_backward_scratch.argtypes = [C.c_int] * 4
-    lib.rdr_sh_reconstruct.restype = C.c_int
-    lib.rdr_sh_reconstruct.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int]
-    lib.rdr_sh_reconstruct_backward.restype = C.c_int
-    lib.rdr_sh_reconstruct_backward.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
-    lib.rdr_envmap_tables.restype = C.c_int
-    lib.rdr_envmap_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int]
-    lib.rdr_mesh_topology_create.restype = C.c_void_p
-    lib.rdr_mesh_topology_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.rdr_mesh_topology_destroy.restype = None
-    lib.rdr_mesh_topology_destroy.argtypes = [C.c_void_p]
-    lib.rdr_mesh_topology_read.restype = C.c_int
-    lib.rdr_mesh_topology_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rdr_vertex_normal_scratch.restype = C.c_int
-    lib.rdr_vertex_normal_scratch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.rdr_vertex_normal.restype = C.c_int
-    lib.rdr_vertex_normal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    lib.rdr_vertex_normal_backward.restype = C.c_int
-    lib.rdr_vertex_normal_backward.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_int64]
-    lib.rdr_debug_trace_plan.restype = C.c_int
-    lib.rdr_debug_trace_plan.argtypes = [C.c_int] * 8 + [C.POINTER(Tuning), C.c_void_p]
-    lib.rdr_debug_scene_trace_plan.restype = C.c_int
-    lib.rdr_debug_scene_trace_plan.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(Tuning), C.c_void_p]
-    lib.rdr_debug_grad_scatter.restype = C.c_int
-    lib.rdr_debug_grad_scatter.argtypes = [C.c_void_p, C.POINTER(DSceneDesc), C.c_uint64, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rdr_debug_compact.restype = C.c_int
-    lib.rdr_debug_compact.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3
-    lib.rdr_debug_walk.restype = C.c_int
-    lib.rdr_debug_walk.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4
-    lib.rdr_debug_sort_pairs.restype = C.c_int
-    lib.rdr_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib, _lib_path = lib, path
     return lib
 

@@ -359,22 +359,12 @@ __global__ void __launch_bounds__(256) inner_area_kernel(const Node *nodes, int 
     if (threadIdx.x == 0) *out = part[0];
 }
 
-inline dim3 grid_of(int n) { return dim3((unsigned)((n + 255) / 256)); }
-template <class T> T *take(BvhDev &d, size_t count) {
-    T *p = (T *)exec::pool_alloc(sizeof(T) * (count ? count : 1));
-    d.owned.push_back(p);
-    return p;
-}
-struct Temp {             // scratch of one build, back to the pool when it ends (the build ends with a synchronisation)
-    std::vector<void *> blocks;
-    template <class T> T *get(size_t count) { T *p = (T *)exec::pool_alloc(sizeof(T) * (count ? count : 1)); blocks.push_back(p); return p; }
-    ~Temp() { for (void *p : blocks) exec::pool_free(p); }
-};
+using exec::grid_of;
 
 // the level loop over prim boxes: fills d.nodes / d.level_first / d.depth and returns the final permutation (slot -> prim)
-int *build_levels(const float *boxes, int n, const BvhBuildParams &prm, BvhDev &d, Temp &tmp) {
+int *build_levels(const float *boxes, int n, const BvhBuildParams &prm, BvhDev &d, rdr::Arena &tmp) {
     hipStream_t st = exec::ctx().stream;
-    d.nodes = take<Node>(d, (size_t)2 * n);
+    d.nodes = d.owned.get<Node>((size_t)2 * n);
     int *perm[2] = {tmp.get<int>(n), tmp.get<int>(n)};
     int *perm_final = tmp.get<int>(n);
     WorkItem *work[2] = {tmp.get<WorkItem>(n), tmp.get<WorkItem>(n)};
@@ -412,11 +402,11 @@ int *build_levels(const float *boxes, int n, const BvhBuildParams &prm, BvhDev &
     return perm_final;
 }
 
-void widen(BvhDev &d, Temp &tmp) {
+void widen(BvhDev &d, rdr::Arena &tmp) {
     hipStream_t st = exec::ctx().stream;
     const int cap = d.num_nodes;
-    d.wide = take<Node4>(d, (size_t)cap);
-    d.wide_src = take<int>(d, (size_t)4 * cap);
+    d.wide = d.owned.get<Node4>((size_t)cap);
+    d.wide_src = d.owned.get<int>((size_t)4 * cap);
     WideItem *items[2] = {tmp.get<WideItem>(cap), tmp.get<WideItem>(cap)};
     WideKids *kids = tmp.get<WideKids>(cap);
     int *rank = tmp.get<int>(cap);
@@ -448,36 +438,36 @@ void widen(BvhDev &d, Temp &tmp) {
 void build_tri_bvh_device(const void *d_shapes, const int *h_prim_ids, int n, const BvhBuildParams &prm, BvhDev &d) {
     if (n <= 0) return;
     hipStream_t st = exec::ctx().stream;
-    Temp tmp;
-    d.prim_ids = take<int>(d, (size_t)2 * n);
+    rdr::Arena tmp;           // scratch of one build, back to the pool when it ends (arena.h)
+    d.prim_ids = d.owned.get<int>((size_t)2 * n);
     exec::upload_async(d.prim_ids, h_prim_ids, sizeof(int) * 2 * n);
     d.shapes = d_shapes;
     float *boxes = tmp.get<float>((size_t)6 * n);
     hipLaunchKernelGGL(tri_boxes_kernel, grid_of(n), dim3(256), 0, st, (const ShapeRef *)d_shapes, d.prim_ids, n, boxes);
     int *perm = build_levels(boxes, n, prm, d, tmp);
     d.num_slots = n;
-    d.tris = take<float>(d, (size_t)9 * n);
-    d.ids = take<int>(d, (size_t)2 * n);
+    d.tris = d.owned.get<float>((size_t)9 * n);
+    d.ids = d.owned.get<int>((size_t)2 * n);
     hipLaunchKernelGGL(tri_gather_kernel, grid_of(n), dim3(256), 0, st, (const ShapeRef *)d_shapes, d.prim_ids, perm, n, d.tris, d.ids);
     widen(d, tmp);
-    d.area = take<double>(d, 1);
+    d.area = d.owned.get<double>(1);
     hipLaunchKernelGGL(inner_area_kernel, dim3(1), dim3(256), 0, st, d.nodes, d.num_nodes, d.area);
     exec::check(hipGetLastError(), "bvh build launch");
-    exec::download(&d.inner_area, d.area, sizeof(double));          // also: the scratch may go back to the pool now
+    exec::download(&d.inner_area, d.area, sizeof(double));          // drains the stream: `tmp` may go back to the pool
 }
 
 void build_box_bvh_device(const float *d_boxes, int n, const BvhBuildParams &prm, BvhDev &d) {
     if (n <= 0) return;
     hipStream_t st = exec::ctx().stream;
-    Temp tmp;
+    rdr::Arena tmp;           // scratch of one build, back to the pool when it ends (arena.h)
     int *perm = build_levels(d_boxes, n, prm, d, tmp);
     d.num_slots = n;
-    d.ids = take<int>(d, (size_t)2 * n);
+    d.ids = d.owned.get<int>((size_t)2 * n);
     hipLaunchKernelGGL(box_ids_kernel, grid_of(n), dim3(256), 0, st, perm, n, d.ids);
-    d.area = take<double>(d, 1);
+    d.area = d.owned.get<double>(1);
     hipLaunchKernelGGL(inner_area_kernel, dim3(1), dim3(256), 0, st, d.nodes, d.num_nodes, d.area);
     exec::check(hipGetLastError(), "bvh build launch");
-    exec::download(&d.inner_area, d.area, sizeof(double));
+    exec::download(&d.inner_area, d.area, sizeof(double));          // drains the stream: `tmp` may go back to the pool
 }
 
 // A Scene with the connectivity of `src`'s: its own copies of the records that hold positions (nodes, triangle records, wide
@@ -488,10 +478,10 @@ void refit_tri_bvh_device(const BvhDev &src, const void *d_shapes, BvhDev &d) { 
     d.num_nodes = src.num_nodes; d.num_slots = src.num_slots; d.depth = src.depth; d.num_wide = src.num_wide;
     d.wide_stack_need = src.wide_stack_need; d.level_first = src.level_first; d.inner_area = src.inner_area;
     d.ids = src.ids; d.wide_src = src.wide_src; d.prim_ids = src.prim_ids; d.shapes = d_shapes;
-    d.nodes = take<Node>(d, (size_t)src.num_nodes);
-    d.tris = take<float>(d, (size_t)9 * src.num_slots);
-    d.wide = take<Node4>(d, (size_t)src.num_wide);
-    d.area = take<double>(d, 1);
+    d.nodes = d.owned.get<Node>((size_t)src.num_nodes);
+    d.tris = d.owned.get<float>((size_t)9 * src.num_slots);
+    d.wide = d.owned.get<Node4>((size_t)src.num_wide);
+    d.area = d.owned.get<double>(1);
     exec::copy_dev(d.nodes, src.nodes, sizeof(Node) * src.num_nodes);          // links + leaf ranges (the boxes are overwritten)
     exec::copy_dev(d.wide, src.wide, sizeof(Node4) * src.num_wide);
     if (d.num_slots > 0)             // (a zero-size grid is a launch error)
@@ -511,8 +501,8 @@ void refit_box_bvh_device(const BvhDev &src, const float *d_boxes, BvhDev &d) {
     d.num_nodes = src.num_nodes; d.num_slots = src.num_slots; d.depth = src.depth;
     d.level_first = src.level_first; d.inner_area = src.inner_area;
     d.ids = src.ids;
-    d.nodes = take<Node>(d, (size_t)src.num_nodes);
-    d.area = take<double>(d, 1);
+    d.nodes = d.owned.get<Node>((size_t)src.num_nodes);
+    d.area = d.owned.get<double>(1);
     exec::copy_dev(d.nodes, src.nodes, sizeof(Node) * src.num_nodes);
     for (int l = (int)d.level_first.size() - 2; l >= 0; --l) {
         const int first = d.level_first[l], end = d.level_first[l + 1];
@@ -522,6 +512,6 @@ void refit_box_bvh_device(const BvhDev &src, const float *d_boxes, BvhDev &d) {
     exec::check(hipGetLastError(), "bvh refit launch");
 }
 
-BvhDev::~BvhDev() { for (void *p : owned) exec::pool_free(p); }
+BvhDev::~BvhDev() {}      // `owned` gives its blocks back
 
 } // namespace rt

@@ -1,6 +1,7 @@
 // bvh_gpu.h -- the hierarchy of bvh.h built / refitted / widened by kernels (bvh_gpu.cpp); what a Scene keeps of it.
 #pragma once
 #include "bvh.h"
+#include "arena.h"
 #include <memory>
 #include <vector>
 
@@ -19,11 +20,9 @@ struct BvhDev {
     std::vector<int> level_first;   // node index at which each level starts, then num_nodes
     double inner_area = 0;          // ... when the topology was built
     std::shared_ptr<const BvhDev> parent;
-    std::vector<void *> owned;
+    rdr::Arena owned;               // the device arrays above that are this tree's own (which also makes the tree non-copyable)
     BvhDev() = default;
-    BvhDev(const BvhDev &) = delete;
-    BvhDev &operator=(const BvhDev &) = delete;
-    ~BvhDev();
+    ~BvhDev();                      // out of line, one definition per backend: bvh_gpu.cpp, and the CPU harness's stand-in for it
     BvhD view() const {
         BvhD v{nodes, tris, ids, num_nodes, num_slots, depth + 2};
         v.wide = wide; v.num_wide = num_wide; v.wide_stack_need = wide_stack_need;

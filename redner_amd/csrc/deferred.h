@@ -18,6 +18,7 @@
 // fp64 is the light-parameter partial sums of the adjoint.
 #pragma once
 #include "../../include/redner_amd.h"
+#include "arena.h"
 #include <cmath>
 #include <stdexcept>
 #include <string>
@@ -389,19 +390,17 @@ inline void validate(const rdr_deferred_desc &d, const char *who) {
     }
 }
 
-// `type` and `range` in memory the launch can read (one block: [L types][2 N range entries]); released by the destructor
+// `type` and `range` in memory the launch can read (one block: [L types][2 N range entries]), back in the pool when the call
+// ends (arena.h: shade / shade_backward end with upload_flush)
 struct Tables {
+    Arena arena;
     int *dev = nullptr;
     Tables(const rdr_deferred_desc &d) {
         std::vector<int> h((size_t)d.num_lights + 2 * (size_t)d.num_images);
         for (int l = 0; l < d.num_lights; ++l) h[l] = d.light_type[l];
         for (int i = 0; i < 2 * d.num_images; ++i) h[d.num_lights + i] = d.image_light_range[i];
-        dev = (int *)exec::pool_alloc(sizeof(int) * h.size());
-        exec::upload_async(dev, h.data(), sizeof(int) * h.size());
+        dev = arena.put(h.data(), h.size());
     }
-    ~Tables() { exec::pool_free(dev); }
-    Tables(const Tables &) = delete;
-    Tables &operator=(const Tables &) = delete;
 };
 
 inline View make_view(const rdr_deferred_desc &d, const Tables &t, const float *g, const float *params) {
@@ -435,15 +434,13 @@ inline void adjoint_impl(const rdr_deferred_desc &d, const View &v, const float 
         if (len > longest) longest = len;
     }
     const int slab_stride = longest * kLightParams;
-    struct Slab {
-        double *p;
-        ~Slab() { exec::pool_free(p); }
-    } slab{(double *)exec::pool_alloc(sizeof(double) * (size_t)per_image * d.num_images * (slab_stride > 0 ? slab_stride : 1))};
+    Arena arena;
+    double *slab = arena.get<double>((size_t)per_image * d.num_images * (slab_stride > 0 ? slab_stride : 1));
     hipLaunchKernelGGL(deferred_adjoint_kernel<C>, dim3(per_image, d.num_images), dim3(256), 0, exec::ctx().stream, v.g, v.params,
-                       v.type, v.range, v.height, v.width, v.aa, d_image, d_g, slab.p, slab_stride);
+                       v.type, v.range, v.height, v.width, v.aa, d_image, d_g, slab, slab_stride);
     exec::check(hipGetLastError(), "deferred_shade_adjoint launch");
     if (d.num_lights > 0) {
-        hipLaunchKernelGGL(deferred_fold_kernel, dim3(d.num_lights), dim3(256), 0, exec::ctx().stream, slab.p, slab_stride, per_image,
+        hipLaunchKernelGGL(deferred_fold_kernel, dim3(d.num_lights), dim3(256), 0, exec::ctx().stream, slab, slab_stride, per_image,
                            v.range, d.num_images, d_params);
         exec::check(hipGetLastError(), "deferred_fold launch");
     }

@@ -448,9 +448,31 @@ struct TreeBuilder {
 
 } // namespace
 
+// rdr_debug_dump_edges: the edge list and, when they are on the host (host builder, or after download_edge_trees), both hierarchies
+void write_edge_dump(FILE *f, const EdgeData *edges) {
+    if (!edges) { fprintf(f, "edges 0\n"); return; }
+    const EdgeData &ed = *edges;
+    fprintf(f, "edges %d\n", (int)ed.edges.size());
+    for (const EdgeD &e : ed.edges) fprintf(f, "%d %d %d %d %d\n", e.shape_id, e.v0, e.v1, e.f0, e.f1);
+    if (!ed.cs_nodes.empty() || !ed.ncs_nodes.empty()) {
+        fprintf(f, "expand %.17g\n", ed.edge_bounds_expand);
+        for (int t = 0; t < 2; ++t) {
+            const std::vector<EdgeNode> &nodes = t == 0 ? ed.cs_nodes : ed.ncs_nodes;
+            int nl = t == 0 ? ed.cs_leaves : ed.ncs_leaves;
+            int nn = (int)nodes.size() - nl;
+            fprintf(f, "%s %d %d\n", t == 0 ? "cs" : "ncs", nl == 0 ? 0 : nn, nl);
+            for (size_t i = 0; i < nodes.size(); ++i) {
+                const EdgeNode &n = nodes[i];
+                fprintf(f, "%d %d %d %d %d %.17g %.17g", (int)i, n.parent, n.child0, n.child1, n.edge_id, n.wlen, n.cost);
+                fprintf(f, " %.17g %.17g %.17g %.17g %.17g %.17g", n.p_min.x, n.p_min.y, n.p_min.z, n.p_max.x, n.p_max.y, n.p_max.z);
+                if (t == 1) fprintf(f, " %.17g %.17g %.17g %.17g %.17g %.17g", n.d_min.x, n.d_min.y, n.d_min.z, n.d_max.x, n.d_max.y, n.d_max.z);
+                fprintf(f, "\n");
+            }
+        }
+    }
+}
+
 void delete_edge_data(EdgeData *e) {
-    if (!e) return;
-    for (void *p : e->owned) exec::pool_free(p);
     delete e;
 }
 
@@ -877,37 +899,31 @@ EdgeData *compute_edge_data(const Scene &scene) {
 // stream; the caller flushes).
 void publish_edge_data(EdgeData &ed) {
     PhaseTimer timer("edge publish");
-    auto up = [&](const void *src, size_t bytes) -> void * {
-        void *p = exec::pool_alloc(bytes);
-        ed.owned.push_back(p);
-        if (bytes) exec::upload_async(p, src, bytes);
-        return p;
-    };
+    auto up = [&](const auto &host) { return ed.owned.put(host.data(), host.size()); };
     EdgeSceneD &d = ed.d;
-    const size_t ne = ed.edges.size();
-    d.edges = (const EdgeD *)up(ed.edges.data(), sizeof(EdgeD) * ne);
-    d.geom = (const EdgeGeom *)up(ed.geom.data(), sizeof(EdgeGeom) * ed.geom.size());
-    d.primary_pmf = ed.primary_pmf.empty() ? nullptr : (const double *)up(ed.primary_pmf.data(), sizeof(double) * ne);
-    d.primary_cdf = ed.primary_cdf.empty() ? nullptr : (const double *)up(ed.primary_cdf.data(), sizeof(double) * ne);
+    d.edges = up(ed.edges);
+    d.geom = up(ed.geom);
+    d.primary_pmf = ed.primary_pmf.empty() ? nullptr : up(ed.primary_pmf);
+    d.primary_cdf = ed.primary_cdf.empty() ? nullptr : up(ed.primary_cdf);
     d.gather = rt::BvhD{nullptr, nullptr, nullptr, 0, 0, 2};
     d.gleaf = nullptr;
     if (!ed.gather.nodes.empty()) {
-        d.gather.nodes = (const rt::Node *)up(ed.gather.nodes.data(), sizeof(rt::Node) * ed.gather.nodes.size());
+        d.gather.nodes = up(ed.gather.nodes);
         d.gather.num_nodes = (int)ed.gather.nodes.size();
         d.gather.num_tris = (int)(ed.gather.ids.size() / 2);
         d.gather.stack_need = ed.gather.depth + 2;
     }
     if (ed.device_trees) {
-        if (d.gather.num_tris > 0) d.gather.ids = (const int *)up(ed.gather.ids.data(), sizeof(int) * ed.gather.ids.size());
+        if (d.gather.num_tris > 0) d.gather.ids = up(ed.gather.ids);
         if (!ed.gather_boxes.empty()) gather_hierarchy_device(ed);
         timer.lap("device copies");
         if (!ed.cs_ids.empty() || !ed.ncs_ids.empty()) build_edge_trees_device(ed);
         timer.lap("hierarchies (device)");
         return;
     }
-    d.cs_nodes = ed.cs_fat.empty() ? nullptr : (const EdgeNodeP *)up(ed.cs_fat.data(), sizeof(EdgeNodeP) * ed.cs_fat.size());
-    d.ncs_nodes = ed.ncs_fat.empty() ? nullptr : (const EdgeNodeP *)up(ed.ncs_fat.data(), sizeof(EdgeNodeP) * ed.ncs_fat.size());
-    if (!ed.gather.nodes.empty()) d.gleaf = (const GatherLeaf *)up(ed.gleaf.data(), sizeof(GatherLeaf) * ed.gleaf.size());
+    d.cs_nodes = ed.cs_fat.empty() ? nullptr : up(ed.cs_fat);
+    d.ncs_nodes = ed.ncs_fat.empty() ? nullptr : up(ed.ncs_fat);
+    if (!ed.gather.nodes.empty()) d.gleaf = up(ed.gleaf);
     timer.lap("device copies");
 }
 

@@ -16,6 +16,7 @@
 #include "surface.h"
 #include "bvh.h"
 #include "bvh_gpu.h"
+#include <cstdio>
 #include <vector>
 
 namespace rdr {
@@ -268,7 +269,7 @@ struct EdgeData {
     std::vector<double> wlen;
     EdgeNode *dev_nodes[2] = {nullptr, nullptr};
     int dev_n[2] = {0, 0};
-    std::vector<void *> owned;                   // device allocations (pool blocks), released by delete_edge_data
+    Arena owned;                                 // device allocations, back in the pool when the structures' last owner lets go
     EdgeSceneD d;            // device view (pointers valid after publish_edge_data)
 };
 // The build in two steps, both run by the edge-builder thread beside the caller (scene.cpp): everything computed on the
@@ -281,6 +282,7 @@ void build_edge_trees_device(EdgeData &ed);
 void drop_gather_cache();                        // the billboard hierarchy kept for the next Scene's refit (rdr_trim_cache)
 void gather_hierarchy_device(EdgeData &ed);      // edges_gpu.cpp: EdgeSceneD::gather from ed.gather_boxes (build or refit, by kernels)
 void download_edge_trees(EdgeData &ed);
+void write_edge_dump(FILE *f, const EdgeData *edges);      // rdr_debug_dump_edges' text; edges == nullptr: no edge sampling
 void delete_edge_data(EdgeData *e);
 // rdr_debug_sort_pairs (include/redner_amd.h): the builder's stable sort of (64-bit code, edge id) pairs on its own; HOST arrays,
 // n >= 1.  edges_gpu.cpp: the radix_* kernels on the calling thread's stream; the CPU debugging harness: std::stable_sort.

@@ -646,7 +646,7 @@ __global__ void __launch_bounds__(256) gather_leaf_kernel(const int *slot_ids, i
     out[sl] = gl;
 }
 
-inline dim3 grid_of(int n) { return dim3((unsigned)((n + 255) / 256)); }
+using exec::grid_of;
 
 }  // namespace
 
@@ -678,14 +678,8 @@ void gather_hierarchy_device(EdgeData &ed) {
     hipStream_t s = exec::ctx().stream;
     const int nc = (int)ed.gather_cur_of.size();
     if (nc == 0) return;
-    auto up = [&](const void *src, size_t bytes) -> void * {
-        void *p = exec::pool_alloc(bytes);
-        ed.owned.push_back(p);
-        exec::upload_async(p, src, bytes);
-        return p;
-    };
-    const float *boxes = (const float *)up(ed.gather_boxes.data(), sizeof(float) * ed.gather_boxes.size());
-    const int *cur_of = (const int *)up(ed.gather_cur_of.data(), sizeof(int) * (size_t)nc);
+    const float *boxes = ed.owned.put(ed.gather_boxes.data(), ed.gather_boxes.size());
+    const int *cur_of = ed.owned.put(ed.gather_cur_of.data(), (size_t)nc);
     auto tree = std::make_shared<rt::BvhDev>();
     bool have = false;
     const int device = exec::current_device();
@@ -708,8 +702,7 @@ void gather_hierarchy_device(EdgeData &ed) {
     }
     if (tree->depth + 2 > 64) throw std::runtime_error("edge gather hierarchy deeper than the traversal stack (64)");
     if ((size_t)tree->num_slots >= ((size_t)1 << 24)) throw std::runtime_error("edge gather hierarchy: more than 2^24 edges are not supported");
-    int *ids = (int *)exec::pool_alloc(sizeof(int) * 2 * (size_t)tree->num_slots);
-    ed.owned.push_back(ids);
+    int *ids = ed.owned.get<int>(2 * (size_t)tree->num_slots);
     hipLaunchKernelGGL(gather_ids_kernel, grid_of(tree->num_slots), dim3(256), 0, s, (const int *)tree->ids, cur_of, tree->num_slots, ids);
     ed.gather_dev = tree;
     ed.d.gather = rt::BvhD{tree->nodes, nullptr, ids, tree->num_nodes, tree->num_slots, tree->depth + 2};
@@ -717,25 +710,19 @@ void gather_hierarchy_device(EdgeData &ed) {
 
 void build_edge_trees_device(EdgeData &ed) {
     hipStream_t s = exec::ctx().stream;
-    auto alloc = [&](size_t bytes) -> void * { void *p = exec::pool_alloc(bytes ? bytes : 16); ed.owned.push_back(p); return p; };
     // what only the build reads (bounds, codes, sort scratch, counters, heights, level lists) goes back to the pool when the
-    // build ends -- after the stream has drained, also when it ends by an exception
-    struct Temporaries {
-        hipStream_t s; std::vector<void *> blocks;
-        ~Temporaries() { (void)hipStreamSynchronize(s); for (void *p : blocks) exec::pool_free(p); }
-    } temporaries{s, {}};
-    auto talloc = [&](size_t bytes) -> void * { void *p = exec::pool_alloc(bytes ? bytes : 16); temporaries.blocks.push_back(p); return p; };
-    auto up = [&](const void *src, size_t bytes) -> void * { void *p = talloc(bytes); if (bytes) exec::upload_async(p, src, bytes); return p; };
+    // build ends (arena.h): the read-back of the flags below drains the stream
+    Arena tmp;
     EdgeSceneD &d = ed.d;
     const int ne = (int)ed.edges.size();
-    Box6D *bounds = (Box6D *)talloc(sizeof(Box6D) * (size_t)ne);
-    const double *wlen = (const double *)up(ed.wlen.data(), sizeof(double) * (size_t)ne);
-    int *leaf_rank = (int *)talloc(sizeof(int) * (size_t)ne);
-    double *leaf_dx = (double *)talloc(sizeof(double) * 2 * (size_t)ne);
+    Box6D *bounds = tmp.get<Box6D>((size_t)ne);
+    const double *wlen = tmp.put(ed.wlen.data(), (size_t)ne);
+    int *leaf_rank = tmp.get<int>((size_t)ne);
+    double *leaf_dx = tmp.get<double>(2 * (size_t)ne);
     // small integers the host reads back: per tree kMaxLevels + 1 level counts; then [0] depth of the 3-D tree, [1] of the
     // 6-D tree, [2] bounds not fp32
     constexpr int kLevelInts = kMaxLevels + 1;
-    int *ints = (int *)talloc(sizeof(int) * (size_t)(4 * kLevelInts + 4));
+    int *ints = tmp.get<int>((size_t)(4 * kLevelInts + 4));
     exec::zero(ints, sizeof(int) * (size_t)(4 * kLevelInts + 4));
     int *level_count[2] = {ints, ints + kLevelInts}, *cursor[2] = {ints + 2 * kLevelInts, ints + 3 * kLevelInts};
     int *flags = ints + 4 * kLevelInts;
@@ -753,27 +740,27 @@ void build_edge_trees_device(EdgeData &ed) {
         ed.dev_nodes[tree] = nullptr; ed.dev_n[tree] = n;
         if (n == 0) continue;
         const int total = t.n_internal + n;
-        const int *ids_in = (const int *)up(ids_h.data(), sizeof(int) * (size_t)n);
+        const int *ids_in = tmp.put(ids_h.data(), (size_t)n);
         const int sb_blocks = std::max(1, std::min(128, n / 2048));
-        Box6D *sb_part = (Box6D *)talloc(sizeof(Box6D) * (size_t)sb_blocks);
-        Box6D *sb = (Box6D *)talloc(sizeof(Box6D));
-        uint64_t *codes_in = (uint64_t *)talloc(sizeof(uint64_t) * (size_t)n), *codes = (uint64_t *)talloc(sizeof(uint64_t) * (size_t)n);
-        int *ids = (int *)talloc(sizeof(int) * (size_t)n);
+        Box6D *sb_part = tmp.get<Box6D>((size_t)sb_blocks);
+        Box6D *sb = tmp.get<Box6D>(1);
+        uint64_t *codes_in = tmp.get<uint64_t>((size_t)n), *codes = tmp.get<uint64_t>((size_t)n);
+        int *ids = tmp.get<int>((size_t)n);
         hipLaunchKernelGGL(scene_bounds_kernel, dim3((unsigned)sb_blocks), dim3(256), 0, s, bounds, ids_in, n, sb_part);
         hipLaunchKernelGGL(scene_bounds_kernel, dim3(1), dim3(256), 0, s, (const Box6D *)sb_part, (const int *)nullptr, sb_blocks, sb);
         hipLaunchKernelGGL(codes_kernel, grid_of(n), dim3(256), 0, s, bounds, ids_in, n, sb, t.is3d, codes_in);
         {
-            uint64_t *codes_tmp = (uint64_t *)talloc(sizeof(uint64_t) * (size_t)n);
-            int *ids_tmp = (int *)talloc(sizeof(int) * (size_t)n);
-            int *hist = (int *)talloc(sizeof(int) * 256 * (size_t)((n + kSortTile - 1) / kSortTile));
+            uint64_t *codes_tmp = tmp.get<uint64_t>((size_t)n);
+            int *ids_tmp = tmp.get<int>((size_t)n);
+            int *hist = tmp.get<int>(256 * (size_t)((n + kSortTile - 1) / kSortTile));
             radix_sort_pairs_u64(s, codes_tmp, ids_tmp, codes_in, ids_in, codes, ids, n, hist);
         }
-        t.nodes = (EdgeNode *)alloc(sizeof(EdgeNode) * (size_t)total);
-        t.below = (int *)talloc(sizeof(int) * (size_t)total);
-        t.counter = (int *)talloc(sizeof(int) * (size_t)total);
-        t.height = (int *)talloc(sizeof(int) * (size_t)total);
+        t.nodes = ed.owned.get<EdgeNode>((size_t)total);
+        t.below = tmp.get<int>((size_t)total);
+        t.counter = tmp.get<int>((size_t)total);
+        t.height = tmp.get<int>((size_t)total);
         t.level_count = level_count[tree];
-        t.level_list = (int *)talloc(sizeof(int) * (size_t)t.n_internal);
+        t.level_list = tmp.get<int>((size_t)t.n_internal);
         t.codes = codes; t.ids = ids;
         ed.dev_nodes[tree] = t.nodes;
         hipLaunchKernelGGL(init_nodes_kernel, grid_of(total), dim3(256), 0, s, t, bounds, wlen);
@@ -801,7 +788,7 @@ void build_edge_trees_device(EdgeData &ed) {
         int run = 0;
         for (int h = 0; h < kMaxLevels; ++h) { h_offsets[(size_t)tree * kMaxLevels + h] = run; run += cnt[h]; if (cnt[h] > 0 && h > top) top = h; }
     }
-    const int *d_offsets = (const int *)up(h_offsets.data(), sizeof(int) * h_offsets.size());
+    const int *d_offsets = tmp.put(h_offsets.data(), h_offsets.size());
     for (int tree = 0; tree < 2; ++tree)
         if (trees[tree].n > 1)
             hipLaunchKernelGGL(level_scatter_kernel, grid_of(trees[tree].n - 1), dim3(256), 0, s, trees[tree], d_offsets + tree * kMaxLevels, cursor[tree]);
@@ -823,7 +810,7 @@ void build_edge_trees_device(EdgeData &ed) {
         const int first_rank = tree == 0 ? (int)ed.ncs_ids.size() : 0;
         hipLaunchKernelGGL(leaf_rank_kernel, grid_of(t.n), dim3(256), 0, s, t, first_rank, tree == 1 ? 1 : 0, leaf_rank, leaf_dx, flags + tree);
         if (t.n > 1) {
-            EdgeNodeP *out = (EdgeNodeP *)alloc(sizeof(EdgeNodeP) * (size_t)(t.n - 1));
+            EdgeNodeP *out = ed.owned.get<EdgeNodeP>((size_t)(t.n - 1));
             hipLaunchKernelGGL(fatten_kernel, grid_of(t.n - 1), dim3(256), 0, s, t, out, flags + 2);
             fat[tree] = out;
             roots[tree] = tree == 0 ? 0 : kEdgeTreeBit;
@@ -834,14 +821,14 @@ void build_edge_trees_device(EdgeData &ed) {
     d.cs_nodes = fat[0]; d.ncs_nodes = fat[1];
     d.cs_root = roots[0]; d.ncs_root = roots[1];
     if (d.gather.num_tris > 0) {
-        GatherLeaf *gl = (GatherLeaf *)alloc(sizeof(GatherLeaf) * (size_t)d.gather.num_tris);
+        GatherLeaf *gl = ed.owned.get<GatherLeaf>((size_t)d.gather.num_tris);
         hipLaunchKernelGGL(gather_leaf_kernel, grid_of(d.gather.num_tris), dim3(256), 0, s, d.gather.ids, d.gather.num_tris, d.geom, leaf_rank, leaf_dx, gl);
         d.gleaf = gl;
     }
     exec::check(hipGetLastError(), "edge hierarchy kernels");
     int h_flags[4] = {0, 0, 0, 0};
     exec::DownloadItem item{h_flags, flags, sizeof(h_flags)};
-    exec::download_batch(&item, 1);
+    exec::download_batch(&item, 1);               // every kernel of the build has finished: `tmp` may go back to the pool
     if (h_flags[2]) throw std::runtime_error("edge hierarchy: spatial bounds are not fp32 values");
     for (int k = 0; k < 2; ++k) {
         if (h_flags[k] == 0) continue;
@@ -870,21 +857,16 @@ void download_edge_trees(EdgeData &ed) {
 void debug_sort_pairs(const uint64_t *keys, const int32_t *vals, int n, uint64_t *keys_out, int32_t *vals_out) {
     if (n < 1 || !keys || !vals || !keys_out || !vals_out) throw std::runtime_error("rdr_debug_sort_pairs: bad arguments");
     hipStream_t s = exec::ctx().stream;
-    struct Temporaries {
-        hipStream_t s; std::vector<void *> blocks;
-        ~Temporaries() { (void)hipStreamSynchronize(s); for (void *p : blocks) exec::pool_free(p); }
-    } temporaries{s, {}};
-    auto talloc = [&](size_t bytes) -> void * { void *p = exec::pool_alloc(bytes); temporaries.blocks.push_back(p); return p; };
+    Arena tmp;
     const size_t kbytes = sizeof(uint64_t) * (size_t)n, vbytes = sizeof(int) * (size_t)n;
-    uint64_t *k_in = (uint64_t *)talloc(kbytes), *k_tmp = (uint64_t *)talloc(kbytes), *k_out = (uint64_t *)talloc(kbytes);
-    int *v_in = (int *)talloc(vbytes), *v_tmp = (int *)talloc(vbytes), *v_out = (int *)talloc(vbytes);
-    int *hist = (int *)talloc(sizeof(int) * 256 * (size_t)((n + kSortTile - 1) / kSortTile));
-    exec::upload(k_in, keys, kbytes);
-    exec::upload(v_in, vals, vbytes);
+    uint64_t *k_in = tmp.put(keys, (size_t)n), *k_tmp = tmp.get<uint64_t>((size_t)n), *k_out = tmp.get<uint64_t>((size_t)n);
+    int *v_in = tmp.put(vals, (size_t)n), *v_tmp = tmp.get<int>((size_t)n), *v_out = tmp.get<int>((size_t)n);
+    int *hist = tmp.get<int>(256 * (size_t)((n + kSortTile - 1) / kSortTile));
+    exec::upload_flush();
     radix_sort_pairs_u64(s, k_tmp, v_tmp, k_in, v_in, k_out, v_out, n, hist);
     exec::check(hipGetLastError(), "radix sort launch");
     exec::download(keys_out, k_out, kbytes);
-    exec::download(vals_out, v_out, vbytes);
+    exec::download(vals_out, v_out, vbytes);              // the sort has finished: `tmp` may go back to the pool
 }
 
 }  // namespace rdr

@@ -1,37 +1,20 @@
-// grad_store.h -- the device arena and the fp64 gradient accumulators of the host driver (render.cpp).
+// grad_store.h -- the fp64 gradient accumulators of the host driver (render.cpp).
 // Included by render.cpp alone: exec::choose_replicas / set_replicas belong to the translation unit that instantiates the
 // stage kernels (hip/exec.h).
 #pragma once
+#include "arena.h"
 #include "scene.h"
 #include "stages_bwd.h"
 #include <algorithm>
-#include <exception>
 #include <stdexcept>
 #include <vector>
 
 namespace rdr {
 
-// Device arena: typed arrays from the caching allocator (exec::pool_alloc); they go back to its free lists when the
-// call ends, so the next render() of the same shape performs no hipMalloc / hipFree at all.
-struct Arena {
-    std::vector<void *> blocks;
-    template <class T> T *get(size_t count) {
-        T *p = (T *)exec::pool_alloc(sizeof(T) * (count ? count : 1));
-        blocks.push_back(p);
-        return p;
-    }
-    // Blocks go back to the pool for ANY stream to reuse: on the normal path render() has drained its streams by then; when the
-    // call ends by an exception, kernels may still be running on them
-    ~Arena() {
-        if (std::uncaught_exceptions() > 0) exec::device_sync();
-        for (void *p : blocks) exec::pool_free(p);
-    }
-};
-
 // ---- gradient accumulators ------------------------------------------------------------------------
 // fp64 mirrors of every tensor in the caller's DScene; folded into the fp32 tensors by flush().
 struct GradStore {
-    Arena arena;
+    Arena arena;               // (arena.h) back in the pool when the call ends: the next render() of the same shape allocates nothing
     GScene g;
     std::vector<GShape> h_shapes;
     std::vector<GMaterial> h_materials;

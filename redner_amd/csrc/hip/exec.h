@@ -246,6 +246,7 @@ inline void copy_dev(void *dst, const void *src, size_t bytes) {          // dev
     if (bytes) check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx().stream), "copy_dev");
 }
 inline void sync() { check(hipStreamSynchronize(ctx().stream), "sync"); }
+inline dim3 grid_of(long long n) { return dim3((unsigned)((n + 255) / 256)); }      // blocks of 256 lanes that cover n items
 constexpr bool kDeviceEdgeTrees = true;         // the edge hierarchies are built by kernels (edges_gpu.cpp)
 constexpr bool kDeviceBvh = true;               // ... and so is the triangle hierarchy (bvh_gpu.cpp)
 __host__ __device__ inline void gather_stats_add(long, long, int, int) {}      // a hook of the CPU debugging harness

@@ -30,6 +30,7 @@
 // kernels agree bit for bit.  fp32 throughout, no contraction.
 #pragma once
 #include "../../include/redner_amd.h"
+#include "arena.h"
 #include <stdexcept>
 #include <string>
 
@@ -415,8 +416,7 @@ inline void pyramid_backward(int height, int width, int channels, int levels, co
                              float *scratch, size_t scratch_count) {
     const Shape s = make_shape(height, width, channels, levels, "rdr_mip_pyramid_backward");
     if (!d_levels || !d_texels) throw std::runtime_error("rdr_mip_pyramid_backward: d_levels and d_texels are required");
-    if (scratch_floats(s) > 0 && (!scratch || scratch_count < scratch_floats(s)))
-        throw std::runtime_error("rdr_mip_pyramid_backward: scratch of " + std::to_string(scratch_floats(s)) + " floats is required");
+    need_scratch("rdr_mip_pyramid_backward", scratch_floats(s), scratch, scratch_count);
     ConstLevels g{};
     Levels acc{};
     for (int l = 0; l < levels; ++l) g.p[l] = d_levels[l];

@@ -1276,23 +1276,15 @@ void debug_grad_scatter(const Scene &scene, const rdr_dscene_desc &ds, size_t jo
         }
     }
 
-    struct Held {                      // released on every path out, also when the launch or a copy throws
-        std::vector<void *> p;
-        void *get(size_t bytes) { p.push_back(nullptr); p.back() = exec::dmalloc(bytes); return p.back(); }
-        ~Held() { exec::device_sync(); for (void *q : p) exec::dfree(q); }
-    } held;
-    unsigned char *d_active = (unsigned char *)held.get(n);
-    double **d_dst = (double **)held.get(sizeof(double *) * n);
-    int *d_shape = (int *)held.get(sizeof(int) * n), *d_tri = (int *)held.get(sizeof(int) * n);
-    double *d_val = (double *)held.get(sizeof(double) * n * width);
-    exec::upload(d_active, active, n);
-    exec::upload(d_dst, h_dst.data(), sizeof(double *) * n);
-    exec::upload(d_shape, h_shape.data(), sizeof(int) * n);
-    exec::upload(d_tri, h_tri.data(), sizeof(int) * n);
-    exec::upload(d_val, values, sizeof(double) * n * width);
+    Arena held;
+    const unsigned char *d_active = held.put(active, n);
+    double *const *d_dst = held.put(h_dst.data(), n);
+    const int *d_shape = held.put(h_shape.data(), n), *d_tri = held.put(h_tri.data(), n);
+    const double *d_val = held.put(values, n * width);
+    exec::upload_flush();
     exec::launch(exec::Count(num_lanes), ScatterProbe{op, plain, d_active, d_dst, d_shape, d_tri, d_val, width, scene.d.shapes, grads.g.shapes});
     grads.flush();
-    exec::sync();
+    exec::sync();                      // the probe and the fold have finished: `held` may go back to the pool
 }
 
 } // namespace rdr

@@ -26,14 +26,6 @@ namespace rdr {
 namespace {
 
 template <class T>
-T *to_device(Scene &s, const T *src, size_t count) {
-    T *p = (T *)exec::pool_alloc(sizeof(T) * (count ? count : 1));
-    s.owned.push_back(p);
-    if (count) exec::upload_async(p, src, sizeof(T) * count);      // create_scene() ends the batch with upload_flush()
-    return p;
-}
-
-template <class T>
 std::vector<T> from_device(const T *src, size_t count) {
     std::vector<T> v(count);
     if (src && count) exec::download(v.data(), src, sizeof(T) * count);
@@ -124,7 +116,44 @@ Scene::~Scene() {
     // a build that is still running reads this Scene's host arrays: wait for it (the structures themselves may live on in
     // the cache / in other Scenes and are released with their last owner)
     if (edge_build.valid()) { try { edge_build.wait(); } catch (...) {} }
-    for (void *p : owned) exec::pool_free(p);
+}
+
+// rdr_debug_bvh_check: the records of the hierarchy the kernels built against the host builder's on the same mesh arrays;
+// returns how many differ
+int compare_bvh_with_host_build(const Scene &s) {
+    std::vector<rt::MeshView> meshes(s.shapes.size());
+    for (size_t i = 0; i < s.shapes.size(); ++i) meshes[i] = rt::MeshView{s.h_vertices[i].data(), s.h_indices[i].data(), s.shapes[i].num_triangles};
+    const rt::BvhHost h = rt::build_bvh(meshes);
+    const rt::BvhDev &d = *s.bvh_dev;
+    int bad = 0;
+    if ((int)h.nodes.size() != d.num_nodes || (int)h.ids.size() != 2 * d.num_slots || (int)h.wide.size() != d.num_wide ||
+        h.depth != d.depth || h.wide_stack_need != d.wide_stack_need)
+        return 1000000 + std::abs((int)h.nodes.size() - d.num_nodes);
+    std::vector<rt::Node> nodes(d.num_nodes);
+    std::vector<int> ids((size_t)2 * d.num_slots);
+    std::vector<float> tris((size_t)9 * d.num_slots);
+    std::vector<rt::Node4> wide(d.num_wide);
+    exec::download(nodes.data(), d.nodes, sizeof(rt::Node) * nodes.size());
+    exec::download(ids.data(), d.ids, sizeof(int) * ids.size());
+    exec::download(tris.data(), d.tris, sizeof(float) * tris.size());
+    exec::download(wide.data(), d.wide, sizeof(rt::Node4) * wide.size());
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        const rt::Node &a = nodes[i], &b = h.nodes[i];
+        bool same = a.a == b.a && a.b == b.b;
+        for (int k = 0; k < 3; ++k) same = same && a.lo[k] == b.lo[k] && a.hi[k] == b.hi[k];
+        bad += !same;
+    }
+    for (size_t i = 0; i < ids.size(); ++i) bad += ids[i] != h.ids[i];
+    for (size_t i = 0; i < tris.size(); ++i) bad += !(tris[i] == h.tris[i]);
+    for (size_t i = 0; i < wide.size(); ++i) {
+        const rt::Node4 &a = wide[i], &b = h.wide[i];
+        bool same = a.aux[0] == b.aux[0];
+        for (int k = 0; k < 4; ++k)
+            same = same && a.link[k] == b.link[k] && a.lox[k] == b.lox[k] && a.loy[k] == b.loy[k] && a.loz[k] == b.loz[k] &&
+                   a.hix[k] == b.hix[k] && a.hiy[k] == b.hiy[k] && a.hiz[k] == b.hiz[k];
+        bad += !same;
+    }
+    return bad;
 }
 
 int compute_num_channels(const int *channels, int n, int max_generic) {
@@ -421,12 +450,12 @@ Scene *create_scene(const rdr_camera_desc *cam, const rdr_shape_desc *shapes, in
                 }
             }
         }
-        const TriGeomD *d_geom = to_device(s, geom.data(), geom.size());
+        const TriGeomD *d_geom = s.owned.put(geom.data(), geom.size());
         for (int i = 0; i < num_shapes; ++i) s.shapes[i].geom = s.shapes[i].num_triangles > 0 ? d_geom + first[i] : nullptr;
     }
-    s.d.shapes = to_device(s, s.shapes.data(), s.shapes.size());
-    s.d.materials = to_device(s, s.materials.data(), s.materials.size());
-    s.d.lights = to_device(s, s.lights.data(), s.lights.size());
+    s.d.shapes = s.owned.put(s.shapes.data(), s.shapes.size());
+    s.d.materials = s.owned.put(s.materials.data(), s.materials.size());
+    s.d.lights = s.owned.put(s.lights.data(), s.lights.size());
     s.d.envmap = nullptr;
     s.d.no_diffs = 0;
     s.d.plain_materials = 0;
@@ -446,15 +475,15 @@ Scene *create_scene(const rdr_camera_desc *cam, const rdr_shape_desc *shapes, in
         e.directly_visible = envmap->directly_visible;
         if (e.values.num_levels > 1) s.has_mipmaps = true;
         s.h_envmap = e;
-        s.d.envmap = to_device(s, &s.h_envmap, 1);
+        s.d.envmap = s.owned.put(&s.h_envmap, 1);
     }
     s.d.num_shapes = num_shapes; s.d.num_materials = num_materials;
     s.d.num_area_lights = num_area_lights; s.d.num_lights = num_lights;
-    s.d.light_pmf = to_device(s, s.light_pmf.data(), s.light_pmf.size());
-    s.d.light_cdf = to_device(s, s.light_cdf.data(), s.light_cdf.size());
-    s.d.light_areas = to_device(s, s.light_areas.data(), s.light_areas.size());
-    s.d.area_cdf_pool = to_device(s, s.area_cdf_pool.data(), s.area_cdf_pool.size());
-    s.d.area_cdf_offset = to_device(s, s.area_cdf_offset.data(), s.area_cdf_offset.size());
+    s.d.light_pmf = s.owned.put(s.light_pmf.data(), s.light_pmf.size());
+    s.d.light_cdf = s.owned.put(s.light_cdf.data(), s.light_cdf.size());
+    s.d.light_areas = s.owned.put(s.light_areas.data(), s.light_areas.size());
+    s.d.area_cdf_pool = s.owned.put(s.area_cdf_pool.data(), s.area_cdf_pool.size());
+    s.d.area_cdf_offset = s.owned.put(s.area_cdf_offset.data(), s.area_cdf_offset.size());
     s.sobol_table = (const uint64_t *)exec::device_constant(rdr_sobol_table, sizeof(uint64_t) * (size_t)kSobolTableWords);
     s.ltc_table = (const float *)exec::device_constant(rdr_ltc_table, sizeof(float) * (size_t)128 * 128 * 9);
 
@@ -504,7 +533,7 @@ Scene *create_scene(const rdr_camera_desc *cam, const rdr_shape_desc *shapes, in
         std::vector<const void *> refs((size_t)2 * std::max(num_shapes, 1), nullptr);
         size_t total = 0;
         for (int i = 0; i < num_shapes; ++i) { refs[2 * i] = s.shapes[i].vertices; refs[2 * i + 1] = s.shapes[i].indices; total += (size_t)s.shapes[i].num_triangles; }
-        const void *d_refs = to_device(s, refs.data(), refs.size());
+        const void *d_refs = s.owned.put(refs.data(), refs.size());
         // (a cached EMPTY hierarchy -- no shapes / no triangles -- is never refitted: there is nothing to gather and a zero-size
         //  launch is an error; the build below returns at once for it)
         bool same = refit_allowed && total > 0 && topo_cache->dev && topo_cache->dev->num_slots > 0 && topo_cache->gpu_index == s.gpu_index &&
@@ -544,12 +573,12 @@ Scene *create_scene(const rdr_camera_desc *cam, const rdr_shape_desc *shapes, in
         s.bvh.num_nodes = (int)s.bvh_host.nodes.size();
         s.bvh.num_tris = (int)s.bvh_host.ids.size() / 2;
         s.bvh.stack_need = s.bvh_host.depth + 2;
-        s.bvh.nodes = to_device(s, s.bvh_host.nodes.data(), s.bvh_host.nodes.size());
-        s.bvh.tris = to_device(s, s.bvh_host.tris.data(), s.bvh_host.tris.size());
-        s.bvh.ids = to_device(s, s.bvh_host.ids.data(), s.bvh_host.ids.size());
+        s.bvh.nodes = s.owned.put(s.bvh_host.nodes.data(), s.bvh_host.nodes.size());
+        s.bvh.tris = s.owned.put(s.bvh_host.tris.data(), s.bvh_host.tris.size());
+        s.bvh.ids = s.owned.put(s.bvh_host.ids.data(), s.bvh_host.ids.size());
         s.bvh.num_wide = (int)s.bvh_host.wide.size();
         s.bvh.wide_stack_need = s.bvh_host.wide_stack_need;
-        s.bvh.wide = s.bvh.num_wide > 0 ? to_device(s, s.bvh_host.wide.data(), s.bvh_host.wide.size()) : nullptr;
+        s.bvh.wide = s.bvh.num_wide > 0 ? s.owned.put(s.bvh_host.wide.data(), s.bvh_host.wide.size()) : nullptr;
         timer.lap("triangle hierarchy (wait)");
     }
     exec::upload_flush();

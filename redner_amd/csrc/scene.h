@@ -86,7 +86,7 @@ struct Scene {
     mutable std::shared_future<std::shared_ptr<EdgeData>> edge_build;   // pending (possibly shared) build, if any
     mutable std::mutex edge_join;                 // edge_data() may be called by several sample workers at once
 
-    std::vector<void *> owned;   // device allocations released in the destructor
+    Arena owned;                 // device allocations; the last member, so the first to go once ~Scene has waited for the build
     ~Scene();
 };
 
@@ -100,5 +100,6 @@ Scene *create_scene(const rdr_camera_desc *camera,
 
 // Channel layout (src/channels.cpp:54-113).  -1 on an unknown channel.
 int compute_num_channels(const int *channels, int n, int max_generic_texture_dimension);
+int compare_bvh_with_host_build(const Scene &s);      // rdr_debug_bvh_check; s.bvh_dev was built (not refitted) by kernels
 
 } // namespace rdr

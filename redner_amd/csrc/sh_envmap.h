@@ -35,6 +35,7 @@
 // the column pass is one lane's walk over H values in a second launch.
 #pragma once
 #include "../../include/redner_amd.h"
+#include "arena.h"
 #include "vecmath.h"
 #include <cmath>
 #include <stdexcept>
@@ -330,9 +331,7 @@ inline void reconstruct_backward(int height, int width, int channels, int num_co
                                  float *d_coeffs, float *scratch, size_t scratch_count) {
     const Plan p = make_plan(height, width, channels, num_coeffs, "rdr_sh_reconstruct_backward");
     if (!clamp || !d_image || !d_coeffs) throw std::runtime_error("rdr_sh_reconstruct_backward: clamp, d_image and d_coeffs are required");
-    if (!scratch || scratch_count < scratch_floats(p) || ((uintptr_t)scratch & 7) != 0)
-        throw std::runtime_error("rdr_sh_reconstruct_backward: scratch of " + std::to_string(scratch_floats(p)) +
-                                 " floats, aligned to 8 bytes, is required");
+    need_scratch("rdr_sh_reconstruct_backward", scratch_floats(p), scratch, scratch_count, true);
     double *partial = reinterpret_cast<double *>(scratch);
     const int tiles = tiles_x(p) * tiles_y(p);
 #if !defined(RDR_HOSTSIM)
@@ -388,14 +387,14 @@ inline void tables(int height, int width, const float *texels, const float *y_we
         throw std::runtime_error("rdr_envmap_tables: texels, y_weight, sample_cdf_ys, sample_cdf_xs and total are required");
 #if !defined(RDR_HOSTSIM)
     hipStream_t stream = exec::ctx().stream;
-    struct Held { float *p = nullptr; ~Held() { if (p) exec::pool_free(p); } } held;
-    held.p = (float *)exec::pool_alloc(sizeof(float));
+    Arena arena;
+    float *sum = arena.get<float>(1);
     hipLaunchKernelGGL(envmap_rows_kernel, dim3((height + kScanRows - 1) / kScanRows), dim3(kThreads), 0, stream, texels, y_weight,
                        height, width, cdf_xs, cdf_ys);
     exec::check(hipGetLastError(), "envmap_rows launch");
-    hipLaunchKernelGGL(envmap_column_kernel, dim3(1), dim3(kThreads), 0, stream, height, cdf_ys, held.p);
+    hipLaunchKernelGGL(envmap_column_kernel, dim3(1), dim3(kThreads), 0, stream, height, cdf_ys, sum);
     exec::check(hipGetLastError(), "envmap_column launch");
-    exec::download(total, held.p, sizeof(float));
+    exec::download(total, sum, sizeof(float));          // both kernels have finished: `arena` may go back to the pool
 #else
     std::vector<float> row(width);
     for (int y = 0; y < height; ++y) {

@@ -54,6 +54,7 @@
 // The per-item bodies are shared with the plain loops of the CPU harness.
 #pragma once
 #include "../../include/redner_amd.h"
+#include "arena.h"
 #include "vecmath.h"
 #include <stdexcept>
 #include <string>
@@ -426,7 +427,6 @@ __global__ void __launch_bounds__(256) vn_gather_kernel(const int *__restrict__ 
     const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (v < (size_t)num_vertices) vertex_gather(offsets, corners, rec, (int)v, d_vertices);
 }
-inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 #endif
 
 // rdr_mesh_topology_create.  `indices` is memory of the plan's place (device memory of gpu_index, or host memory for the
@@ -457,7 +457,7 @@ inline Topology *create_topology(const int *indices, int num_triangles, int num_
             exec::zero(counts, sizeof(int) * ((size_t)num_vertices + 1));
             exec::copy_dev(t->indices, indices, sizeof(int) * (size_t)num_corners);
             if (num_corners > 0) {
-                hipLaunchKernelGGL(vn_count_kernel, dim3(blocks(num_corners)), dim3(256), 0, stream, t->indices, num_corners, num_vertices,
+                hipLaunchKernelGGL(vn_count_kernel, exec::grid_of(num_corners), dim3(256), 0, stream, t->indices, num_corners, num_vertices,
                                    counts, counts + num_vertices);
                 exec::check(hipGetLastError(), "vn_count launch");
             }
@@ -467,10 +467,10 @@ inline Topology *create_topology(const int *indices, int num_triangles, int num_
             hipLaunchKernelGGL(vn_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, counts, num_vertices, t->offsets);
             exec::check(hipGetLastError(), "vn_scan launch");
             if (num_corners > 0) {
-                hipLaunchKernelGGL(vn_scatter_kernel, dim3(blocks(num_corners)), dim3(256), 0, stream, t->indices, num_corners,
+                hipLaunchKernelGGL(vn_scatter_kernel, exec::grid_of(num_corners), dim3(256), 0, stream, t->indices, num_corners,
                                    num_vertices, t->offsets, counts, t->corners);
                 exec::check(hipGetLastError(), "vn_scatter launch");
-                hipLaunchKernelGGL(vn_sort_kernel, dim3(blocks(num_vertices)), dim3(256), 0, stream, t->offsets, num_vertices, t->corners);
+                hipLaunchKernelGGL(vn_sort_kernel, exec::grid_of(num_vertices), dim3(256), 0, stream, t->offsets, num_vertices, t->corners);
                 exec::check(hipGetLastError(), "vn_sort launch");
             }
             exec::sync();                        // `counts` is released below
@@ -516,22 +516,17 @@ inline size_t forward_scratch_floats(const Topology &t, bool cot) { return (size
 inline size_t backward_scratch_floats(const Topology &t, bool) { return (size_t)9 * t.num_triangles; }
 inline size_t saved_floats(const Topology &t, bool cot) { return (size_t)3 * t.num_vertices * (cot ? 2 : 1); }
 
-inline void need_scratch(const char *who, size_t need, const float *scratch, size_t have) {
-    if (need > 0 && (!scratch || have < need))
-        throw std::runtime_error(std::string(who) + ": scratch of " + std::to_string(need) + " floats is required");
-}
-
 template <bool COT>
 inline void forward_impl(const Topology &t, const float *vertices, float *normals, float *saved, float *scratch) {
     float *contrib = scratch, *cot = COT ? scratch + (size_t)9 * t.num_triangles : nullptr;
 #if !defined(RDR_HOSTSIM)
     hipStream_t stream = exec::ctx().stream;
     if (t.num_triangles > 0) {
-        hipLaunchKernelGGL(vn_face_kernel<COT>, dim3(blocks(t.num_triangles)), dim3(256), 0, stream, vertices, t.indices, t.num_triangles,
+        hipLaunchKernelGGL(vn_face_kernel<COT>, exec::grid_of(t.num_triangles), dim3(256), 0, stream, vertices, t.indices, t.num_triangles,
                            contrib, cot);
         exec::check(hipGetLastError(), "vn_face launch");
     }
-    hipLaunchKernelGGL(vn_vertex_kernel<COT>, dim3(blocks(t.num_vertices)), dim3(256), 0, stream, t.offsets, t.corners, contrib, cot,
+    hipLaunchKernelGGL(vn_vertex_kernel<COT>, exec::grid_of(t.num_vertices), dim3(256), 0, stream, t.offsets, t.corners, contrib, cot,
                        t.num_vertices, normals, saved);
     exec::check(hipGetLastError(), "vn_vertex launch");
 #else
@@ -546,11 +541,11 @@ inline void backward_impl(const Topology &t, const float *vertices, const float 
 #if !defined(RDR_HOSTSIM)
     hipStream_t stream = exec::ctx().stream;
     if (t.num_triangles > 0) {
-        hipLaunchKernelGGL(vn_face_adjoint_kernel<COT>, dim3(blocks(t.num_triangles)), dim3(256), 0, stream, vertices, t.indices, saved,
+        hipLaunchKernelGGL(vn_face_adjoint_kernel<COT>, exec::grid_of(t.num_triangles), dim3(256), 0, stream, vertices, t.indices, saved,
                            d_normals, t.num_vertices, t.num_triangles, rec);
         exec::check(hipGetLastError(), "vn_face_adjoint launch");
     }
-    hipLaunchKernelGGL(vn_gather_kernel, dim3(blocks(t.num_vertices)), dim3(256), 0, stream, t.offsets, t.corners, rec, t.num_vertices,
+    hipLaunchKernelGGL(vn_gather_kernel, exec::grid_of(t.num_vertices), dim3(256), 0, stream, t.offsets, t.corners, rec, t.num_vertices,
                        d_vertices);
     exec::check(hipGetLastError(), "vn_gather launch");
 #else

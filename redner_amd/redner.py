@@ -329,19 +329,16 @@ class Scene:                           # src/redner.cpp:62-73
                  use_primary_edge_sampling, use_secondary_edge_sampling):
         lib = _capi.lib()
         self._lib = lib
-        _use_torch_stream(lib, use_gpu, gpu_index)
         self.camera = camera
         sh = (_capi.ShapeDesc * max(len(shapes), 1))(*[s._desc for s in shapes])
         mt = (_capi.MaterialDesc * max(len(materials), 1))(*[m._to_desc() for m in materials])
         al = (_capi.AreaLightDesc * max(len(area_lights), 1))(*[l._desc for l in area_lights])
         env = C.byref(envmap._desc) if envmap is not None else None
         self._refs = (camera, shapes, materials, area_lights, envmap)
-        self._handle = lib.rdr_scene_create(C.byref(camera._desc), sh, len(shapes), mt, len(materials),
-                                            al, len(area_lights), env, int(bool(use_gpu)), int(gpu_index),
-                                            int(bool(use_primary_edge_sampling)),
-                                            int(bool(use_secondary_edge_sampling)))
-        if not self._handle:
-            raise RuntimeError('redner.Scene: ' + _capi.last_error())
+        self._handle = _call(lib, 'Scene', 'rdr_scene_create', C.byref(camera._desc), sh, len(shapes), mt, len(materials),
+                             al, len(area_lights), env, int(bool(use_gpu)), int(gpu_index),
+                             int(bool(use_primary_edge_sampling)), int(bool(use_secondary_edge_sampling)),
+                             on=(use_gpu, gpu_index), ok=bool)
         self.max_generic_texture_dimension = lib.rdr_scene_max_generic_texture_dimension(self._handle)
         self.use_gpu, self.gpu_index = bool(use_gpu), int(gpu_index)
 
@@ -402,12 +399,9 @@ def render(scene, options, rendered_image, d_rendered_image, d_scene, screen_gra
     """redner.render(...)  src/redner.cpp:257 -- forward iff rendered_image != 0, backward iff
     d_rendered_image != 0."""
     od = options._to_desc()
-    _use_torch_stream(scene._lib, scene.use_gpu, scene.gpu_index)
     ds = C.byref(d_scene._desc) if d_scene is not None else None
-    rc = scene._lib.rdr_render(scene._handle, C.byref(od), _addr(rendered_image), _addr(d_rendered_image), ds,
-                               _addr(screen_gradient_image), _addr(debug_image))
-    if rc != 0:
-        raise RuntimeError('redner.render: ' + _capi.last_error())
+    _call(scene._lib, 'render', 'rdr_render', scene._handle, C.byref(od), _addr(rendered_image), _addr(d_rendered_image), ds,
+          _addr(screen_gradient_image), _addr(debug_image), on=(scene.use_gpu, scene.gpu_index))
 
 
 class DeferredLightType(enum.IntEnum):     # rdr_deferred_light_type (not in the reference's module: its deferred lights are torch code)
@@ -427,7 +421,7 @@ def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, im
         raise RuntimeError('redner.deferred_shade: %d light ranges for %d images' % (len(image_light_ranges), d.num_images))
     ranges = (C.c_int32 * max(len(flat), 1))(*flat)
     d.light_type, d.image_light_range = types, ranges
-    d.gpu_index = int(gpu_index) if use_gpu else -1
+    d.gpu_index = _place(use_gpu, gpu_index)
     return d, (types, ranges)
 
 
@@ -436,22 +430,17 @@ def deferred_shade(g_buffer, light_params, image, num_images, height, width, aa_
     """Not in the reference: rdr_deferred_shade (include/redner_amd.h).  g_buffer [N, H * aa, W * aa, 9 + alpha],
     light_params [L, 10], image [N, H, W, 3 + alpha]: float_ptr; light_types: L DeferredLightType; image_light_ranges: N
     (begin, end) pairs into the table."""
-    lib = _capi.lib()
     d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index)
-    _use_torch_stream(lib, use_gpu, gpu_index)
-    if lib.rdr_deferred_shade(C.byref(d), _addr(g_buffer), _addr(light_params), _addr(image)) != 0:
-        raise RuntimeError('redner.deferred_shade: ' + _capi.last_error())
+    _call(_capi.lib(), 'deferred_shade', 'rdr_deferred_shade', C.byref(d), _addr(g_buffer), _addr(light_params), _addr(image),
+          on=(use_gpu, gpu_index))
 
 
 def deferred_shade_backward(g_buffer, light_params, d_image, d_g_buffer, d_light_params, num_images, height, width,
                             aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index):
     """Not in the reference: rdr_deferred_shade_backward; writes every element of d_g_buffer and d_light_params."""
-    lib = _capi.lib()
     d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index)
-    _use_torch_stream(lib, use_gpu, gpu_index)
-    if lib.rdr_deferred_shade_backward(C.byref(d), _addr(g_buffer), _addr(light_params), _addr(d_image), _addr(d_g_buffer),
-                                       _addr(d_light_params)) != 0:
-        raise RuntimeError('redner.deferred_shade_backward: ' + _capi.last_error())
+    _call(_capi.lib(), 'deferred_shade_backward', 'rdr_deferred_shade_backward', C.byref(d), _addr(g_buffer), _addr(light_params),
+          _addr(d_image), _addr(d_g_buffer), _addr(d_light_params), on=(use_gpu, gpu_index))
 
 
 def mip_num_levels(height, width):
@@ -461,19 +450,15 @@ def mip_num_levels(height, width):
 
 def mip_backward_scratch(height, width, channels):
     """Not in the reference's module: floats of scratch mip_pyramid_backward needs for an image of this size."""
-    n = int(_capi.lib().rdr_mip_backward_scratch(int(height), int(width), int(channels)))
-    if n < 0:
-        raise RuntimeError('redner.mip_backward_scratch: ' + _capi.last_error())
-    return n
+    return int(_call(_capi.lib(), 'mip_backward_scratch', 'rdr_mip_backward_scratch', int(height), int(width), int(channels),
+                     ok=_not_negative))
 
 
 def mip_tiled_stages(height, width, channels):
     """Not in the reference's module: how many tiled launches (three levels each) mip_pyramid and mip_pyramid_backward make for an
     image of this size before one workgroup does the rest (csrc/mipmap.h: tiled_stages); 0 = one workgroup does everything."""
-    n = int(_capi.lib().rdr_mip_tiled_stages(int(height), int(width), int(channels)))
-    if n < 0:
-        raise RuntimeError('redner.mip_tiled_stages: ' + _capi.last_error())
-    return n
+    return int(_call(_capi.lib(), 'mip_tiled_stages', 'rdr_mip_tiled_stages', int(height), int(width), int(channels),
+                     ok=_not_negative))
 
 
 def _level_table(levels):
@@ -484,62 +469,47 @@ def mip_pyramid(levels, height, width, channels, use_gpu, gpu_index):
     """Not in the reference's module (its pyramid is torch code, pyredner/texture.py): rdr_mip_pyramid (include/redner_amd.h).
     levels: float_ptr of every level, [0] the image [height, width, channels]; levels 1.. are written.  Ordered on the
     current torch stream, not synchronised."""
-    lib = _capi.lib()
-    _use_torch_stream(lib, use_gpu, gpu_index)
-    if lib.rdr_mip_pyramid(int(height), int(width), int(channels), len(levels), _level_table(levels),
-                           int(gpu_index) if use_gpu else -1) != 0:
-        raise RuntimeError('redner.mip_pyramid: ' + _capi.last_error())
+    _call(_capi.lib(), 'mip_pyramid', 'rdr_mip_pyramid', int(height), int(width), int(channels), len(levels), _level_table(levels),
+          _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def mip_pyramid_backward(d_levels, d_texels, scratch, scratch_floats, height, width, channels, use_gpu, gpu_index):
     """Not in the reference's module: rdr_mip_pyramid_backward.  d_levels: float_ptr per level, float_ptr(0) = zeros; writes every
     element of d_texels."""
-    lib = _capi.lib()
-    _use_torch_stream(lib, use_gpu, gpu_index)
-    if lib.rdr_mip_pyramid_backward(int(height), int(width), int(channels), len(d_levels), _level_table(d_levels), _addr(d_texels),
-                                    _addr(scratch), int(scratch_floats), int(gpu_index) if use_gpu else -1) != 0:
-        raise RuntimeError('redner.mip_pyramid_backward: ' + _capi.last_error())
+    _call(_capi.lib(), 'mip_pyramid_backward', 'rdr_mip_pyramid_backward', int(height), int(width), int(channels), len(d_levels),
+          _level_table(d_levels), _addr(d_texels), _addr(scratch), int(scratch_floats), _place(use_gpu, gpu_index),
+          on=(use_gpu, gpu_index))
 
 
 def sh_backward_scratch(height, width, channels, num_coeffs):
     """Not in the reference's module: floats of scratch sh_reconstruct_backward needs (rdr_sh_backward_scratch)."""
-    n = int(_capi.lib().rdr_sh_backward_scratch(int(height), int(width), int(channels), int(num_coeffs)))
-    if n < 0:
-        raise RuntimeError('redner.sh_backward_scratch: ' + _capi.last_error())
-    return n
+    return int(_call(_capi.lib(), 'sh_backward_scratch', 'rdr_sh_backward_scratch', int(height), int(width), int(channels),
+                     int(num_coeffs), ok=_not_negative))
 
 
 def sh_reconstruct(coeffs, image, clamp, channels, num_coeffs, height, width, use_gpu, gpu_index):
     """Not in the reference's module (its SH_reconstruct is torch code, pyredner/utils.py): rdr_sh_reconstruct
     (include/redner_amd.h).  coeffs: float_ptr of [channels, num_coeffs]; writes image [height, width, channels] and, unless it
     is None, the clamp bytes.  Ordered on the current torch stream, not synchronised."""
-    lib = _capi.lib()
-    _use_torch_stream(lib, use_gpu, gpu_index)
-    if lib.rdr_sh_reconstruct(_addr(coeffs) or None, int(channels), int(num_coeffs), int(height), int(width), _addr(image) or None,
-                              _addr(clamp) or None, int(gpu_index) if use_gpu else -1) != 0:
-        raise RuntimeError('redner.sh_reconstruct: ' + _capi.last_error())
+    _call(_capi.lib(), 'sh_reconstruct', 'rdr_sh_reconstruct', _addr(coeffs) or None, int(channels), int(num_coeffs), int(height),
+          int(width), _addr(image) or None, _addr(clamp) or None, _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def sh_reconstruct_backward(clamp, d_image, d_coeffs, scratch, scratch_floats, channels, num_coeffs, height, width, use_gpu,
                             gpu_index):
     """Not in the reference's module: rdr_sh_reconstruct_backward.  Writes every element of d_coeffs [channels, num_coeffs]."""
-    lib = _capi.lib()
-    _use_torch_stream(lib, use_gpu, gpu_index)
-    if lib.rdr_sh_reconstruct_backward(_addr(clamp) or None, _addr(d_image) or None, int(channels), int(num_coeffs), int(height),
-                                       int(width), _addr(d_coeffs) or None, _addr(scratch) or None, int(scratch_floats),
-                                       int(gpu_index) if use_gpu else -1) != 0:
-        raise RuntimeError('redner.sh_reconstruct_backward: ' + _capi.last_error())
+    _call(_capi.lib(), 'sh_reconstruct_backward', 'rdr_sh_reconstruct_backward', _addr(clamp) or None, _addr(d_image) or None,
+          int(channels), int(num_coeffs), int(height), int(width), _addr(d_coeffs) or None, _addr(scratch) or None,
+          int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def envmap_tables(texels, y_weight, sample_cdf_ys, sample_cdf_xs, height, width, use_gpu, gpu_index):
     """Not in the reference's module (its tables are torch code, pyredner/envmap.py): rdr_envmap_tables.  float_ptr arguments;
     writes both tables and returns the last unnormalised entry of the column table (one synchronisation)."""
-    lib = _capi.lib()
-    _use_torch_stream(lib, use_gpu, gpu_index)
     total = C.c_float(0.0)
-    if lib.rdr_envmap_tables(_addr(texels) or None, _addr(y_weight) or None, int(height), int(width), _addr(sample_cdf_ys) or None,
-                             _addr(sample_cdf_xs) or None, C.byref(total), int(gpu_index) if use_gpu else -1) != 0:
-        raise RuntimeError('redner.envmap_tables: ' + _capi.last_error())
+    _call(_capi.lib(), 'envmap_tables', 'rdr_envmap_tables', _addr(texels) or None, _addr(y_weight) or None, int(height), int(width),
+          _addr(sample_cdf_ys) or None, _addr(sample_cdf_xs) or None, C.byref(total), _place(use_gpu, gpu_index),
+          on=(use_gpu, gpu_index))
     return float(total.value)
 
 
@@ -559,11 +529,8 @@ class mesh_topology:
         self.lib, self.handle = _capi.lib(), None
         self.num_triangles, self.num_vertices = int(num_triangles), int(num_vertices)
         self.use_gpu, self.gpu_index = bool(use_gpu), int(gpu_index)
-        _use_torch_stream(self.lib, use_gpu, gpu_index)
-        self.handle = self.lib.rdr_mesh_topology_create(_addr(indices) or None, self.num_triangles, self.num_vertices,
-                                                        int(self.use_gpu), self.gpu_index)
-        if not self.handle:
-            raise RuntimeError('redner.mesh_topology: ' + _capi.last_error())
+        self.handle = _call(self.lib, 'mesh_topology', 'rdr_mesh_topology_create', _addr(indices) or None, self.num_triangles,
+                            self.num_vertices, int(self.use_gpu), self.gpu_index, on=(use_gpu, gpu_index), ok=bool)
 
     def destroy(self):
         if self.handle:
@@ -576,39 +543,51 @@ class mesh_topology:
         except Exception:
             pass
 
-    def _error(self, what):
-        return RuntimeError('redner.%s: %s' % (what, self.lib.rdr_last_error().decode()))
-
     def read(self):
         """(offsets [V + 1], corners [3 T]) as lists: the rows of the plan (tests)."""
         offsets, corners = (C.c_int * (self.num_vertices + 1))(), (C.c_int * max(3 * self.num_triangles, 1))()
-        if self.lib.rdr_mesh_topology_read(self.handle, offsets, corners) != 0:
-            raise self._error('mesh_topology.read')
+        _call(self.lib, 'mesh_topology.read', 'rdr_mesh_topology_read', self.handle, offsets, corners)
         return list(offsets), list(corners)[:3 * self.num_triangles]
 
     def scratch(self, scheme):
         """floats of (forward scratch, backward scratch, saved) for a weighting scheme (rdr_vertex_normal_scratch)."""
         counts = [C.c_int64(0) for _ in range(3)]
-        if self.lib.rdr_vertex_normal_scratch(self.handle, int(scheme), *[C.byref(c) for c in counts]) != 0:
-            raise self._error('mesh_topology.scratch')
+        _call(self.lib, 'mesh_topology.scratch', 'rdr_vertex_normal_scratch', self.handle, int(scheme), *[C.byref(c) for c in counts])
         return tuple(int(c.value) for c in counts)
 
 
 def vertex_normal(topology, scheme, vertices, normals, saved, scratch, scratch_floats):
     """Not in the reference's module (its compute_vertex_normal is torch code, pyredner/shape.py): rdr_vertex_normal.  float_ptr
     arguments; writes normals [V, 3] and saved.  Ordered on the current torch stream, not synchronised."""
-    _use_torch_stream(topology.lib, topology.use_gpu, topology.gpu_index)
-    if topology.lib.rdr_vertex_normal(topology.handle, int(scheme), _addr(vertices), _addr(normals), _addr(saved),
-                                      _addr(scratch) or None, int(scratch_floats)) != 0:
-        raise topology._error('vertex_normal')
+    _call(topology.lib, 'vertex_normal', 'rdr_vertex_normal', topology.handle, int(scheme), _addr(vertices), _addr(normals),
+          _addr(saved), _addr(scratch) or None, int(scratch_floats), on=(topology.use_gpu, topology.gpu_index))
 
 
 def vertex_normal_backward(topology, scheme, vertices, saved, d_normals, d_vertices, scratch, scratch_floats):
     """Not in the reference's module: rdr_vertex_normal_backward.  Writes every element of d_vertices [V, 3]."""
-    _use_torch_stream(topology.lib, topology.use_gpu, topology.gpu_index)
-    if topology.lib.rdr_vertex_normal_backward(topology.handle, int(scheme), _addr(vertices), _addr(saved), _addr(d_normals),
-                                               _addr(d_vertices), _addr(scratch) or None, int(scratch_floats)) != 0:
-        raise topology._error('vertex_normal_backward')
+    _call(topology.lib, 'vertex_normal_backward', 'rdr_vertex_normal_backward', topology.handle, int(scheme), _addr(vertices),
+          _addr(saved), _addr(d_normals), _addr(d_vertices), _addr(scratch) or None, int(scratch_floats),
+          on=(topology.use_gpu, topology.gpu_index))
+
+
+def _place(use_gpu, gpu_index):
+    """The gpu_index argument of the C ABI: negative = host memory (the CPU debugging harness only)."""
+    return int(gpu_index) if use_gpu else -1
+
+
+def _not_negative(n):
+    return n >= 0
+
+
+def _call(lib, what, name, *args, on=None, ok=lambda rc: rc == 0):
+    """One checked call of the C ABI on `lib`: ordered on the current torch stream of on = (use_gpu, gpu_index) if given;
+    a result that is not `ok` raises with the text of THAT library (another one may have been loaded since the handle was made)."""
+    if on is not None:
+        _use_torch_stream(lib, *on)
+    result = getattr(lib, name)(*args)
+    if not ok(result):
+        raise RuntimeError('redner.%s: %s' % (what, lib.rdr_last_error().decode('utf-8', 'replace')))
+    return result
 
 
 def _use_torch_stream(lib, use_gpu, gpu_index=None):

@@ -60,3 +60,68 @@ def test_missing_library_is_an_error(tmp_path):
     from redner_amd import _capi
     with pytest.raises(RuntimeError, match='not found'):
         _capi.load(str(tmp_path / 'nope.so'))
+
+
+def declared_signatures():
+    """name -> number of parameters, for every rdr_* function include/redner_amd.h declares"""
+    src = open(HEADER).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    src = re.sub(r'//[^\n]*', '', src)
+    found = {}
+    for name, params in re.findall(r'\b(rdr_[a-z_0-9]+)\s*\(([^()]*)\)\s*;', src):
+        params = params.strip()
+        found[name] = 0 if params in ('', 'void') else len(params.split(','))
+    return found
+
+
+def test_signature_table_matches_the_header():
+    """Every declared function has a (restype, argtypes) entry of the right length and there is no entry without a declaration: a
+    forgotten signature would send 64-bit handles through ctypes' default int conversion."""
+    from redner_amd import _capi
+    declared = declared_signatures()
+    assert len(declared) == 43
+    assert set(declared) == set(_capi.SIGNATURES) == set(_capi.EXPORTS)
+    for name, count in declared.items():
+        restype, argtypes = _capi.SIGNATURES[name]
+        assert len(argtypes) == count, name
+
+
+def _null_handles_are_errors(lib, tmp_path):
+    """The entry points that used to dereference a null Scene report it; a call that succeeds clears the text.  No kernel runs."""
+    def error():
+        return lib.rdr_last_error().decode()
+
+    assert lib.rdr_scene_trace(None, None, None, 0, 0) == 1 and 'rdr_scene_trace' in error()
+    assert lib.rdr_debug_bvh_check(None) == -2 and 'rdr_debug_bvh_check' in error()
+    path = tmp_path / 'edges.txt'
+    assert lib.rdr_debug_dump_edges(None, str(path).encode()) == 1 and 'rdr_debug_dump_edges' in error()
+    assert not path.exists()
+    assert lib.rdr_render(None, None, None, None, None, None, None) == 1
+    assert error() == 'rdr_render: scene and options are required'
+    out = (ctypes.c_int32 * 10)()
+    assert lib.rdr_debug_trace_plan(1000, 24, 1, 20, 1000, 0, 0, 0, None, out) == 0       # host arithmetic only
+    assert error() == ''
+
+
+def test_null_handles_are_errors_harness(hostsim_backend, tmp_path):
+    from redner_amd import _capi
+    _null_handles_are_errors(_capi.lib(), tmp_path)
+
+
+@pytest.mark.gpu
+def test_null_handles_are_errors_product(gpu_backend, tmp_path):
+    from redner_amd import _capi
+    _null_handles_are_errors(_capi.lib(), tmp_path)
+
+
+def test_arena_rule(tmp_path):
+    """csrc/arena.h over a counting stand-in for exec.h (tests/arena), as a program of its own under ASan + UBSan: blocks go
+    back when the owner dies, and only an owner that dies during stack unwinding waits for the device first."""
+    import subprocess
+    exe = str(tmp_path / 'arena_rule')
+    subprocess.check_call(['g++', '-std=c++17', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
+                           '-I' + os.path.join(ROOT, 'tests', 'arena'), '-I' + os.path.join(ROOT, 'redner_amd', 'csrc'),
+                           os.path.join(ROOT, 'tests', 'arena', 'arena_rule.cpp'), '-o', exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert 'arena rule ok' in r.stdout

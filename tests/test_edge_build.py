@@ -27,7 +27,6 @@ def _dump(backend, builder, path, is_oracle, device=torch.device('cpu')):
     else:
         from redner_amd import _capi
         lib = _capi.lib()
-        lib.rdr_debug_dump_edges.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
         assert lib.rdr_debug_dump_edges(u.scene._handle, path.encode()) == 0
 
 
