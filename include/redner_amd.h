@@ -365,6 +365,9 @@ int rdr_vertex_normal(const rdr_mesh_topology *topology, int scheme, const float
 int rdr_vertex_normal_backward(const rdr_mesh_topology *topology, int scheme, const float *vertices, const float *saved,
                                const float *d_normals, float *d_vertices, float *scratch, int64_t scratch_floats);
 
+/* Laplacian smoothing on the plan above (rdr_mesh_boundary, rdr_mesh_smooth_scratch, rdr_mesh_laplacian, rdr_mesh_laplacian_backward,
+ * rdr_mesh_smooth) is declared in its own header, redner_amd_mesh.h, which includes this one. */
+
 /* Message of the last failure on the calling thread ("" if none). */
 const char *rdr_last_error(void);
 

@@ -11,7 +11,8 @@
     redner_amd.utils             SH_reconstruct on the native spherical-harmonic kernels (a coefficient gradient included):
                                  `from redner_amd import SH_reconstruct`
     redner_amd.shape             compute_vertex_normal on the native vertex-normal kernels (a vertex gradient included):
-                                 `from redner_amd import compute_vertex_normal, MeshTopology`
+                                 `from redner_amd import compute_vertex_normal, MeshTopology`; smooth / bound_vertices and
+                                 the differentiable mesh_laplacian on the native smoothing kernels, on the same plan
     redner_amd.install()         register redner_amd.redner as `redner` for the reference's
                                  unmodified pyredner package
 """
@@ -21,7 +22,7 @@ _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLigh
                  'deferred_shade', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo', 'render_pathtracing')
 _TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid', 'envmap_sampling_tables')
 _UTILS = ('SH_reconstruct', 'SHReconstruct')
-_SHAPE = ('compute_vertex_normal', 'MeshTopology', 'VertexNormals')
+_SHAPE = ('compute_vertex_normal', 'MeshTopology', 'VertexNormals', 'smooth', 'mesh_laplacian', 'bound_vertices', 'MeshLaplacian')
 
 
 def __getattr__(name):

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/redner_amd.h.
+"""ctypes binding of the C ABI in include/redner_amd.h and its companion include/redner_amd_mesh.h.
 
 The shared library is the product: `redner_amd/lib/libredner_amd.so`, built by
 `__graft_entry__.build()` (hipcc, gfx950).  If it is missing the import fails loudly -- there is
@@ -194,6 +194,15 @@ SIGNATURES = {
     'rdr_debug_sort_pairs': (_i, [_p, _p, _i, _p, _p]),
 }
 EXPORTS = tuple(SIGNATURES)
+# Every symbol of include/redner_amd_mesh.h, the companion header (Laplacian smoothing, csrc/mesh_smooth.h): the same form, the same
+# library; load() requires and binds them like the ones above (tests/test_mesh_smooth.py compares this table with that header).
+MESH_SIGNATURES = {
+    'rdr_mesh_boundary': (_i, [_p, _p]),
+    'rdr_mesh_smooth_scratch': (_i, [_p, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    'rdr_mesh_laplacian': (_i, [_p, _i, _p, _p, _p, _p, _p, _i64]),
+    'rdr_mesh_laplacian_backward': (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64]),
+    'rdr_mesh_smooth': (_i, [_p, _i, _p, _p, C.c_float, _i, _p, _p, _i64]),
+}
 
 # rdr_scatter_op / rdr_scatter_target (rdr_debug_grad_scatter)
 SCATTER_ACCUM, SCATTER_ACCUM_TEXEL, SCATTER_ACCUM_PLAIN, SCATTER_ACCUM_TRIPLE, SCATTER_ACCUM_TEXEL_TRIPLE, \
@@ -216,10 +225,10 @@ def load(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % path)
     lib = C.CDLL(path)
-    for name in EXPORTS:
+    for name in EXPORTS + tuple(MESH_SIGNATURES):
         if not hasattr(lib, name):
             raise RuntimeError("redner_amd: %s does not export %s" % (path, name))
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib, _lib_path = lib, path

@@ -7,6 +7,7 @@
 #include "deferred.h"
 #include "mipmap.h"
 #include "vertex_normal.h"
+#include "mesh_smooth.h"
 #include "sh_envmap.h"
 #include <cstdio>
 #include "scene.h"
@@ -311,6 +312,53 @@ int rdr_vertex_normal_backward(const rdr_mesh_topology *topology, int scheme, co
         const rdr::vnrm::Topology &t = topology_of(topology, "rdr_vertex_normal_backward");
         OnDevice on(t.gpu_index, "rdr_vertex_normal_backward");
         rdr::vnrm::backward(t, scheme, vertices, saved, d_normals, d_vertices, scratch, floats(scratch_floats));
+    });
+}
+
+// ---- Laplacian smoothing (csrc/mesh_smooth.h) ----
+int rdr_mesh_boundary(const rdr_mesh_topology *topology, float *bound) {
+    return status([&] {
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_mesh_boundary");
+        OnDevice on(t.gpu_index, "rdr_mesh_boundary");
+        rdr::msm::boundary(t, bound);
+    });
+}
+
+int rdr_mesh_smooth_scratch(const rdr_mesh_topology *topology, int scheme, int64_t *forward_floats, int64_t *backward_floats,
+                            int64_t *saved_floats) {
+    return status([&] {
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_mesh_smooth_scratch");
+        rdr::msm::scheme_of(scheme, "rdr_mesh_smooth_scratch");
+        if (forward_floats) *forward_floats = (int64_t)rdr::msm::forward_scratch_floats(t);
+        if (backward_floats) *backward_floats = (int64_t)rdr::msm::backward_scratch_floats(t);
+        if (saved_floats) *saved_floats = (int64_t)rdr::msm::saved_floats(t);
+    });
+}
+
+int rdr_mesh_laplacian(const rdr_mesh_topology *topology, int scheme, const float *vertices, const float *control, float *shift,
+                       float *saved, float *scratch, int64_t scratch_floats) {
+    return status([&] {
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_mesh_laplacian");
+        OnDevice on(t.gpu_index, "rdr_mesh_laplacian");
+        rdr::msm::laplacian(t, scheme, vertices, control, shift, saved, scratch, floats(scratch_floats));
+    });
+}
+
+int rdr_mesh_laplacian_backward(const rdr_mesh_topology *topology, int scheme, const float *vertices, const float *control,
+                                const float *saved, const float *d_shift, float *d_vertices, float *scratch, int64_t scratch_floats) {
+    return status([&] {
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_mesh_laplacian_backward");
+        OnDevice on(t.gpu_index, "rdr_mesh_laplacian_backward");
+        rdr::msm::laplacian_backward(t, scheme, vertices, control, saved, d_shift, d_vertices, scratch, floats(scratch_floats));
+    });
+}
+
+int rdr_mesh_smooth(const rdr_mesh_topology *topology, int scheme, const float *vertices_in, const float *control, float lmd,
+                    int iterations, float *vertices_out, float *scratch, int64_t scratch_floats) {
+    return status([&] {
+        const rdr::vnrm::Topology &t = topology_of(topology, "rdr_mesh_smooth");
+        OnDevice on(t.gpu_index, "rdr_mesh_smooth");
+        rdr::msm::smooth(t, scheme, vertices_in, control, lmd, iterations, vertices_out, scratch, floats(scratch_floats));
     });
 }
 

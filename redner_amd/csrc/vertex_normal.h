@@ -127,6 +127,11 @@ RDR_FN float corner_angle(const Corner &c) {
     const float as = (float)gm::atan2(x, sqrt((1.0 - x) * (1.0 + x)));
     return c.obtuse ? kPi - 2.0f * as : 2.0f * as;
 }
+// 1 / tan(angle) of a spread corner
+RDR_FN float cotangent_of(float angle) {
+    const float tangent = (float)(gm::sin((double)angle) / gm::cos((double)angle));
+    return 1.0f / tangent;
+}
 
 // A face: its three corner records.  contrib[3 c ..] = the 'max' addend of corner c; cot[3 c ..] = w of corner c.
 template <bool COT>
@@ -146,8 +151,7 @@ RDR_FN void face_forward(const float *vertices, const int *indices, int f, float
             const float angle = corner_angle(c);
             add = n * ((float)gm::sin((double)angle) / c.e1e2);
             if (COT && c.spread) {
-                const float tangent = (float)(gm::sin((double)angle) / gm::cos((double)angle));
-                w = (p2 - p1) * (1.0f / tangent);
+                w = (p2 - p1) * cotangent_of(angle);
             }
         }
         store3(contrib + 3 * (c0 + k), add);
@@ -230,6 +234,25 @@ RDR_FN SumGrad vertex_adjoint(const float *saved, const float *d_normals, int v,
     return d;
 }
 
+// A spread corner i of a face, cot_i = (e1 . e2) / |e1 x e2|: adds to dp[0 .. 3) the position gradient of a loss whose
+// derivative with respect to the vector (p[i+2] - p[i+1]) cot_i is h and whose derivative with respect to cot_i, the edge held,
+// is u (h . (p[i+2] - p[i+1]), plus whatever else the caller hangs on cot_i: mesh_smooth.h).  Nothing where |e1 x e2| == 0.
+RDR_FN void cotangent_corner_adjoint(const D3 *P, int i, D3 h, double u, D3 *dp) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+    const D3 e1 = P[i1] - P[i], e2 = P[i2] - P[i], Mi = cross(e1, e2);
+    const double S = sqrt(dot(Mi, Mi)), D = dot(e1, e2);
+    if (!(S > 0.0)) return;
+    const D3 through = h * (D / S);
+    dp[i2] = dp[i2] + through;
+    dp[i1] = dp[i1] - through;
+    const double dD = u / S, dS = -u * D / (S * S);
+    const D3 dM = Mi * (dS / S);
+    const D3 de1 = e2 * dD + cross(e2, dM), de2 = e1 * dD + cross(dM, e1);
+    dp[i1] = dp[i1] + de1;
+    dp[i2] = dp[i2] + de2;
+    dp[i] = dp[i] - (de1 + de2);
+}
+
 // A face: rec[3 c ..] = d loss / d position of the vertex at corner c through this face (all three corners' terms).
 template <bool COT>
 RDR_FN void face_adjoint(const float *vertices, const int *indices, const float *saved, const float *d_normals, int num_vertices,
@@ -279,20 +302,8 @@ RDR_FN void face_adjoint(const float *vertices, const int *indices, const float 
         for (int i = 0; i < 3; ++i) {
             if (!corner[i].spread) continue;
             const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
-            const D3 e1 = P[i1] - P[i], e2 = P[i2] - P[i], Mi = cross(e1, e2);
-            const double S = sqrt(dot(Mi, Mi)), D = dot(e1, e2);
-            if (!(S > 0.0)) continue;
             const D3 h = gcot[i1] - gcot[i2];
-            const double u = dot(h, P[i2] - P[i1]);
-            const D3 through = h * (D / S);
-            dp[i2] = dp[i2] + through;
-            dp[i1] = dp[i1] - through;
-            const double dD = u / S, dS = -u * D / (S * S);
-            const D3 dM = Mi * (dS / S);
-            const D3 de1 = e2 * dD + cross(e2, dM), de2 = e1 * dD + cross(dM, e1);
-            dp[i1] = dp[i1] + de1;
-            dp[i2] = dp[i2] + de2;
-            dp[i] = dp[i] - (de1 + de2);
+            cotangent_corner_adjoint(P, i, h, dot(h, P[i2] - P[i1]), dp);
         }
     }
 #pragma unroll

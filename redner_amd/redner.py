@@ -570,6 +570,48 @@ def vertex_normal_backward(topology, scheme, vertices, saved, d_normals, d_verti
           on=(topology.use_gpu, topology.gpu_index))
 
 
+class SmoothWeighting(enum.IntEnum):
+    """Not in the reference's module: rdr_smooth_weighting, the weighting_scheme strings of pyredner.smooth."""
+    reciprocal = 0
+    uniform = 1
+    cotangent = 2
+
+
+def mesh_smooth_scratch(topology, scheme):
+    """Not in the reference's module: floats of (forward scratch, backward scratch, saved) of a smoothing scheme
+    (rdr_mesh_smooth_scratch); mesh_smooth needs the forward scratch."""
+    counts = [C.c_int64(0) for _ in range(3)]
+    _call(topology.lib, 'mesh_smooth_scratch', 'rdr_mesh_smooth_scratch', topology.handle, int(scheme), *[C.byref(c) for c in counts])
+    return tuple(int(c.value) for c in counts)
+
+
+def mesh_boundary(topology, bound):
+    """Not in the reference's module (its bound_vertices is torch code, pyredner/shape.py): rdr_mesh_boundary.  Writes bound [V]."""
+    _call(topology.lib, 'mesh_boundary', 'rdr_mesh_boundary', topology.handle, _addr(bound), on=(topology.use_gpu, topology.gpu_index))
+
+
+def mesh_laplacian(topology, scheme, vertices, control, shift, saved, scratch, scratch_floats):
+    """Not in the reference's module (its smooth is torch code, pyredner/shape.py): rdr_mesh_laplacian.  float_ptr arguments;
+    control: float_ptr(0) = all 1; writes shift [V, 3] and saved.  Ordered on the current torch stream, not synchronised."""
+    _call(topology.lib, 'mesh_laplacian', 'rdr_mesh_laplacian', topology.handle, int(scheme), _addr(vertices), _addr(control) or None,
+          _addr(shift), _addr(saved), _addr(scratch) or None, int(scratch_floats), on=(topology.use_gpu, topology.gpu_index))
+
+
+def mesh_laplacian_backward(topology, scheme, vertices, control, saved, d_shift, d_vertices, scratch, scratch_floats):
+    """Not in the reference's module: rdr_mesh_laplacian_backward.  Writes every element of d_vertices [V, 3]."""
+    _call(topology.lib, 'mesh_laplacian_backward', 'rdr_mesh_laplacian_backward', topology.handle, int(scheme), _addr(vertices),
+          _addr(control) or None, _addr(saved), _addr(d_shift), _addr(d_vertices), _addr(scratch) or None, int(scratch_floats),
+          on=(topology.use_gpu, topology.gpu_index))
+
+
+def mesh_smooth(topology, scheme, vertices_in, control, lmd, iterations, vertices_out, scratch, scratch_floats):
+    """Not in the reference's module: rdr_mesh_smooth, `iterations` steps vertices + shift * lmd (lmd rounded to fp32).  Writes
+    every element of vertices_out [V, 3], which may be vertices_in."""
+    _call(topology.lib, 'mesh_smooth', 'rdr_mesh_smooth', topology.handle, int(scheme), _addr(vertices_in), _addr(control) or None,
+          float(lmd), int(iterations), _addr(vertices_out), _addr(scratch) or None, int(scratch_floats),
+          on=(topology.use_gpu, topology.gpu_index))
+
+
 def _place(use_gpu, gpu_index):
     """The gpu_index argument of the C ABI: negative = host memory (the CPU debugging harness only)."""
     return int(gpu_index) if use_gpu else -1

@@ -1,4 +1,5 @@
-"""Smooth vertex normals (pyredner/shape.py: compute_vertex_normal) on the native kernels, with a vertex gradient.
+"""Smooth vertex normals (pyredner/shape.py: compute_vertex_normal) on the native kernels, with a vertex gradient; and, further
+down, Laplacian smoothing (smooth, bound_vertices, the differentiable mesh_laplacian) on the same plan.
 
     topology = MeshTopology(indices, num_vertices)                   # once per connectivity
     for it in range(steps):
@@ -139,3 +140,118 @@ def compute_vertex_normal(vertices, indices, weighting_scheme='max', topology=No
     if topology is None:
         topology = _cached_topology(indices, int(vertices.shape[0]), backend or _default_backend)
     return VertexNormals.apply(vertices, topology, SCHEMES[weighting_scheme])
+
+
+# ---- Laplacian smoothing (pyredner/shape.py: bound_vertices, smooth; csrc/mesh_smooth.h restates the meaning) ---------------------
+#   * every vertex i gets a vector sum C_i and a weight sum W_i over its corners ('reciprocal': unit sides and 1 / |side|;
+#     'uniform': sides and 2; 'cotangent': the opposite edges times cot of the opposite angles, and those cots);
+#     shift_i = (C_i / W_i) * control_i, and smooth sets v_i = v_i + shift_i * lmd
+#   * per-corner terms in fp32, per-vertex sums in fp64 in ascending corner id, rounded once: bitwise reproducible (the
+#     reference's scatter_add_ is fp32 atomics on a GPU)
+#   * a vertex with W == 0 (isolated, or of degenerate corners only) does not move and has a zero gradient, and a 'cotangent'
+#     corner that is degenerate adds nothing, where the reference returns NaN
+#   * mesh_laplacian is the displacement itself as a differentiable function (a regulariser |L v|^2 can go into a loss);
+#     the reference's smooth only updates vertices.data
+SMOOTH_SCHEMES = {'reciprocal': 0, 'uniform': 1, 'cotangent': 2}
+
+
+def _smooth_arguments(who, vertices, indices, weighting_scheme, topology, backend):
+    """The checks of compute_vertex_normal for the smoothing functions -> the topology"""
+    if weighting_scheme not in SMOOTH_SCHEMES:
+        raise ValueError('Unknown weighting_scheme: {}'.format(weighting_scheme))
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise RuntimeError('%s: vertices must be a [V, 3] tensor' % who)
+    if topology is None:
+        topology = _cached_topology(indices, int(vertices.shape[0]), backend or _default_backend)
+    if tuple(vertices.shape) != (topology.num_vertices, 3):
+        raise RuntimeError('%s: vertices must be [%d, 3], got %s' % (who, topology.num_vertices, tuple(vertices.shape)))
+    if vertices.dtype != torch.float32:
+        raise RuntimeError('%s: fp32 vertices only' % who)
+    if vertices.device != topology.device:
+        raise RuntimeError('%s: vertices are on %s, the topology on %s' % (who, vertices.device, topology.device))
+    return topology
+
+
+def _boundary(topology):
+    rd = topology.rd
+    bound = torch.empty(topology.num_vertices, dtype=torch.float32, device=topology.device)
+    rd.mesh_boundary(topology.native, rd.float_ptr(bound.data_ptr()))
+    return bound
+
+
+def _control(control, topology):
+    """control [V] as the kernels read it: fp32, contiguous, on the topology's device, a constant; None = the boundary mask"""
+    if control is None:
+        return _boundary(topology)
+    if not isinstance(control, torch.Tensor) or control.numel() != topology.num_vertices:
+        raise ValueError('Size of control tensor inconsistent with number of vertices')
+    return control.detach().to(device=topology.device, dtype=torch.float32).reshape(-1).contiguous()
+
+
+def bound_vertices(vertices, indices, topology=None, backend=None):
+    """pyredner.bound_vertices: [V] fp32 on the vertices' device, 0 for a vertex on an open rim of the mesh, otherwise 1 (the
+    default `control` of smooth).  A function of the connectivity only, summed in integers.  topology: as compute_vertex_normal."""
+    return _boundary(_smooth_arguments('bound_vertices', vertices, indices, 'reciprocal', topology, backend))
+
+
+class MeshLaplacian(torch.autograd.Function):
+    """vertices [V, 3] -> shift [V, 3] = (C / W) * control; control [V] is a constant.  One native call forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, vertices, topology, scheme, control):
+        rd = topology.rd
+        v = vertices.detach().contiguous()
+        n_fwd, _, n_saved = rd.mesh_smooth_scratch(topology.native, scheme)
+        shift = torch.empty_like(v)
+        saved = torch.empty(max(n_saved, 1), dtype=torch.float32, device=v.device)
+        scratch = torch.empty(max(n_fwd, 1), dtype=torch.float32, device=v.device)
+        rd.mesh_laplacian(topology.native, scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(control.data_ptr()),
+                          rd.float_ptr(shift.data_ptr()), rd.float_ptr(saved.data_ptr()), rd.float_ptr(scratch.data_ptr()), n_fwd)
+        ctx.topology, ctx.scheme = topology, scheme
+        ctx.save_for_backward(v, control, saved)
+        ctx.set_materialize_grads(False)
+        return shift
+
+    @staticmethod
+    def backward(ctx, d_shift):
+        if d_shift is None:
+            return None, None, None, None
+        topology, rd = ctx.topology, ctx.topology.rd
+        v, control, saved = ctx.saved_tensors
+        g = d_shift.to(device=v.device, dtype=torch.float32).contiguous()
+        n_bwd = rd.mesh_smooth_scratch(topology.native, ctx.scheme)[1]
+        d_vertices = torch.empty_like(v)
+        scratch = torch.empty(max(n_bwd, 1), dtype=torch.float32, device=v.device)
+        rd.mesh_laplacian_backward(topology.native, ctx.scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(control.data_ptr()),
+                                   rd.float_ptr(saved.data_ptr()), rd.float_ptr(g.data_ptr()), rd.float_ptr(d_vertices.data_ptr()),
+                                   rd.float_ptr(scratch.data_ptr()), n_bwd)
+        return d_vertices, None, None, None
+
+
+def mesh_laplacian(vertices, indices, weighting_scheme='reciprocal', control=None, topology=None, backend=None):
+    """The displacement of one smoothing step of unit length, [V, 3] fp32 (contiguous, on the vertices' device), differentiable
+    with respect to `vertices`: smooth(vertices, ..., lmd) adds mesh_laplacian(vertices, ...) * lmd.  weighting_scheme:
+    'reciprocal', 'uniform' or 'cotangent'.  control: [V] factors, a constant; None = bound_vertices (an open rim stays put).
+    topology: as compute_vertex_normal."""
+    topology = _smooth_arguments('mesh_laplacian', vertices, indices, weighting_scheme, topology, backend)
+    return MeshLaplacian.apply(vertices, topology, SMOOTH_SCHEMES[weighting_scheme], _control(control, topology))
+
+
+def smooth(vertices, indices, lmd, weighting_scheme='reciprocal', control=None, topology=None, iterations=1, backend=None):
+    """pyredner.smooth: `iterations` steps of Laplacian smoothing, vertices += mesh_laplacian(vertices) * lmd, written into the
+    tensor's own memory.  Returns None and leaves no autograd record (a leaf that requires grad is accepted and stays a leaf);
+    vertices._version advances, so whatever is cached by version sees the change.  lmd: a Python number or a one-element tensor,
+    rounded to fp32.  control: as mesh_laplacian, evaluated once for all iterations."""
+    topology = _smooth_arguments('smooth', vertices, indices, weighting_scheme, topology, backend)
+    if int(iterations) < 1:
+        raise ValueError('smooth: iterations must be at least 1, got %s' % (iterations,))
+    rd, scheme = topology.rd, SMOOTH_SCHEMES[weighting_scheme]
+    control = _control(control, topology)
+    v = vertices.detach().contiguous()
+    n_fwd = rd.mesh_smooth_scratch(topology.native, scheme)[0]
+    moved = torch.empty_like(v)
+    scratch = torch.empty(max(n_fwd, 1), dtype=torch.float32, device=v.device)
+    rd.mesh_smooth(topology.native, scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(control.data_ptr()), float(lmd), int(iterations),
+                   rd.float_ptr(moved.data_ptr()), rd.float_ptr(scratch.data_ptr()), n_fwd)
+    with torch.no_grad():
+        vertices.copy_(moved)              # (not a write through .data: that would leave vertices._version where it was)
