@@ -13,6 +13,9 @@
     redner_amd.shape             compute_vertex_normal on the native vertex-normal kernels (a vertex gradient included):
                                  `from redner_amd import compute_vertex_normal, MeshTopology`; smooth / bound_vertices and
                                  the differentiable mesh_laplacian on the native smoothing kernels, on the same plan
+    redner_amd.loss              gaussian_pyramid_loss, the image pyramid loss of the reference's optimisation scripts, on the
+                                 native pyramid-loss kernels (an image gradient included):
+                                 `from redner_amd import gaussian_pyramid_loss, GaussianPyramidLoss`
     redner_amd.install()         register redner_amd.redner as `redner` for the reference's
                                  unmodified pyredner package
 """
@@ -22,6 +25,7 @@ _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLigh
                  'deferred_shade', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo', 'render_pathtracing')
 _TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid', 'envmap_sampling_tables')
 _UTILS = ('SH_reconstruct', 'SHReconstruct')
+_LOSS = ('gaussian_pyramid_loss', 'GaussianPyramidLoss')
 _SHAPE = ('compute_vertex_normal', 'MeshTopology', 'VertexNormals', 'smooth', 'mesh_laplacian', 'bound_vertices', 'MeshLaplacian')
 
 
@@ -39,6 +43,9 @@ def __getattr__(name):
     if name in _UTILS:
         from . import utils
         return getattr(utils, name)
+    if name in _LOSS:
+        from . import loss
+        return getattr(loss, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 

@@ -203,6 +203,14 @@ MESH_SIGNATURES = {
     'rdr_mesh_laplacian_backward': (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64]),
     'rdr_mesh_smooth': (_i, [_p, _i, _p, _p, C.c_float, _i, _p, _p, _i64]),
 }
+# Every symbol of include/redner_amd_image.h, the second companion header (the Gaussian pyramid loss, csrc/pyramid_loss.h): the same
+# form again (tests/test_pyramid_loss.py compares this table with that header).
+IMAGE_SIGNATURES = {
+    'rdr_pyramid_loss_scratch': (_i, [_i] * 5 + [C.POINTER(_i64), C.POINTER(_i64)]),
+    'rdr_pyramid_loss_plan': (_i, [_i] * 5 + [C.POINTER(_i), C.POINTER(_i)]),
+    'rdr_pyramid_loss': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _p, _p, _i64, _i]),
+    'rdr_pyramid_loss_backward': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _i64, _p, _p, _p, _p, _i64, _i]),
+}
 
 # rdr_scatter_op / rdr_scatter_target (rdr_debug_grad_scatter)
 SCATTER_ACCUM, SCATTER_ACCUM_TEXEL, SCATTER_ACCUM_PLAIN, SCATTER_ACCUM_TRIPLE, SCATTER_ACCUM_TEXEL_TRIPLE, \
@@ -225,10 +233,10 @@ def load(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % path)
     lib = C.CDLL(path)
-    for name in EXPORTS + tuple(MESH_SIGNATURES):
+    for name in EXPORTS + tuple(MESH_SIGNATURES) + tuple(IMAGE_SIGNATURES):
         if not hasattr(lib, name):
             raise RuntimeError("redner_amd: %s does not export %s" % (path, name))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib, _lib_path = lib, path

@@ -9,6 +9,7 @@
 #include "vertex_normal.h"
 #include "mesh_smooth.h"
 #include "sh_envmap.h"
+#include "pyramid_loss.h"
 #include <cstdio>
 #include "scene.h"
 #include <cstring>
@@ -256,6 +257,45 @@ int rdr_envmap_tables(const float *texels, const float *y_weight, int height, in
     return status([&] {
         OnDevice on(gpu_index, "rdr_envmap_tables");
         rdr::shenv::tables(height, width, texels, y_weight, sample_cdf_ys, sample_cdf_xs, total);
+    });
+}
+
+// ---- the Gaussian pyramid loss (csrc/pyramid_loss.h, include/redner_amd_image.h) ----
+int rdr_pyramid_loss_scratch(int batch, int height, int width, int channels, int num_levels, int64_t *forward_floats,
+                             int64_t *backward_floats) {
+    return status([&] {
+        const rdr::pyl::Plan p = rdr::pyl::make_plan(batch, height, width, channels, num_levels, nullptr, 0.f, "rdr_pyramid_loss_scratch");
+        if (forward_floats) *forward_floats = (int64_t)rdr::pyl::forward_floats(p);
+        if (backward_floats) *backward_floats = (int64_t)rdr::pyl::backward_floats(p);
+    });
+}
+
+int rdr_pyramid_loss_plan(int batch, int height, int width, int channels, int num_levels, int *tiled_levels, int *small_floats) {
+    return status([&] {
+        const rdr::pyl::Plan p = rdr::pyl::make_plan(batch, height, width, channels, num_levels, nullptr, 0.f, "rdr_pyramid_loss_plan");
+        if (tiled_levels) *tiled_levels = p.tiled;
+        if (small_floats) *small_floats = rdr::pyl::kSmall;
+    });
+}
+
+int rdr_pyramid_loss(const float *image, const float *target, int batch, int height, int width, int channels, int num_levels,
+                     const float *weights, float clamp, float *loss, double *terms, float *scratch, int64_t scratch_floats,
+                     int gpu_index) {
+    return status([&] {
+        OnDevice on(gpu_index, "rdr_pyramid_loss");
+        const rdr::pyl::Plan p = rdr::pyl::make_plan(batch, height, width, channels, num_levels, weights, clamp, "rdr_pyramid_loss");
+        rdr::pyl::forward(p, image, target, loss, terms, scratch, floats(scratch_floats));
+    });
+}
+
+int rdr_pyramid_loss_backward(const float *image, const float *target, int batch, int height, int width, int channels,
+                              int num_levels, const float *weights, float clamp, const float *saved, int64_t saved_floats,
+                              const float *upstream, float *d_image, float *d_target, float *scratch, int64_t scratch_floats,
+                              int gpu_index) {
+    return status([&] {
+        OnDevice on(gpu_index, "rdr_pyramid_loss_backward");
+        const rdr::pyl::Plan p = rdr::pyl::make_plan(batch, height, width, channels, num_levels, weights, clamp, "rdr_pyramid_loss_backward");
+        rdr::pyl::backward(p, image, target, saved, floats(saved_floats), upstream, d_image, d_target, scratch, floats(scratch_floats));
     });
 }
 

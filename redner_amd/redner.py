@@ -503,6 +503,47 @@ def sh_reconstruct_backward(clamp, d_image, d_coeffs, scratch, scratch_floats, c
           int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
+def pyramid_loss_scratch(batch, height, width, channels, num_levels):
+    """Not in the reference's module: (forward_floats, backward_floats), the scratch pyramid_loss and pyramid_loss_backward need
+    (rdr_pyramid_loss_scratch, include/redner_amd_image.h)."""
+    fwd, bwd = C.c_int64(0), C.c_int64(0)
+    _call(_capi.lib(), 'pyramid_loss_scratch', 'rdr_pyramid_loss_scratch', int(batch), int(height), int(width), int(channels),
+          int(num_levels), C.byref(fwd), C.byref(bwd))
+    return int(fwd.value), int(bwd.value)
+
+
+def pyramid_loss_plan(batch, height, width, channels, num_levels):
+    """Not in the reference's module: (tiled_levels, small_floats) of rdr_pyramid_loss_plan: how many leading levels the tiled
+    kernels do, and the floats per image at or below which a level is left to the one workgroup per image (csrc/pyramid_loss.h)."""
+    tiled, small = C.c_int(0), C.c_int(0)
+    _call(_capi.lib(), 'pyramid_loss_plan', 'rdr_pyramid_loss_plan', int(batch), int(height), int(width), int(channels),
+          int(num_levels), C.byref(tiled), C.byref(small))
+    return int(tiled.value), int(small.value)
+
+
+def _weight_table(weights, num_levels):
+    return None if weights is None else (C.c_float * max(int(num_levels), 1))(*[float(w) for w in weights])
+
+
+def pyramid_loss(image, target, loss, terms, scratch, scratch_floats, batch, height, width, channels, num_levels, weights, clamp,
+                 use_gpu, gpu_index):
+    """Not in the reference's module (its scripts write the loss in torch): rdr_pyramid_loss.  image, target, loss, scratch:
+    float_ptr; terms: the address of num_levels doubles or None; weights: num_levels numbers or None; clamp: 0 = none.  Ordered
+    on the current torch stream, not synchronised."""
+    _call(_capi.lib(), 'pyramid_loss', 'rdr_pyramid_loss', _addr(image) or None, _addr(target) or None, int(batch), int(height),
+          int(width), int(channels), int(num_levels), _weight_table(weights, num_levels), float(clamp), _addr(loss) or None,
+          _addr(terms) or None, _addr(scratch) or None, int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+
+
+def pyramid_loss_backward(image, target, saved, saved_floats, upstream, d_image, d_target, scratch, scratch_floats, batch, height,
+                          width, channels, num_levels, weights, clamp, use_gpu, gpu_index):
+    """Not in the reference's module: rdr_pyramid_loss_backward.  Writes every element of d_image and, unless None, d_target."""
+    _call(_capi.lib(), 'pyramid_loss_backward', 'rdr_pyramid_loss_backward', _addr(image) or None, _addr(target) or None, int(batch),
+          int(height), int(width), int(channels), int(num_levels), _weight_table(weights, num_levels), float(clamp),
+          _addr(saved) or None, int(saved_floats), _addr(upstream) or None, _addr(d_image) or None, _addr(d_target) or None,
+          _addr(scratch) or None, int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+
+
 def envmap_tables(texels, y_weight, sample_cdf_ys, sample_cdf_xs, height, width, use_gpu, gpu_index):
     """Not in the reference's module (its tables are torch code, pyredner/envmap.py): rdr_envmap_tables.  float_ptr arguments;
     writes both tables and returns the last unnormalised entry of the column table (one synchronisation)."""
