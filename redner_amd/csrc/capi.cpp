@@ -28,8 +28,10 @@ thread_local std::string g_last_error;
 // devices run side by side (one host thread per device in one process): every piece of state they touch is per device (buffer
 // pool free lists, Scene caches, helper threads, streams, compaction scratch) or per host thread (stream, tuning, staging), and
 // what is shared (host thread pool, edge-builder thread, trace statistics) has its own lock.
-std::recursive_mutex g_device_lock[16];
-std::recursive_mutex &device_lock(int gpu_index) { return g_device_lock[(gpu_index < 0 ? 0 : gpu_index) & 15]; }
+rdr::PerDevice<std::recursive_mutex> g_device_lock;
+std::recursive_mutex &device_lock(int gpu_index) { return g_device_lock.at(gpu_index); }      // where a caller's index enters: may throw
+// ... of a handle's own device, for its destroyer: the index passed device_lock when the handle was made, nothing can throw
+std::recursive_mutex &lock_of_handle(int gpu_index) noexcept { return g_device_lock.slot[gpu_index < 0 ? 0 : gpu_index]; }
 // rdr_set_stream: the stream the calling thread's launches are ordered on (null = the null stream)
 thread_local void *g_user_stream = nullptr;
 
@@ -161,7 +163,7 @@ void rdr_scene_destroy(rdr_scene *scene) {
     rdr::Scene *s = reinterpret_cast<rdr::Scene *>(scene);
     // under the device's lock like every other call that touches its pool / caches (the destructor returns buffers and may join
     // the Scene's edge build)
-    std::lock_guard<std::recursive_mutex> lk(device_lock(s->gpu_index));
+    std::lock_guard<std::recursive_mutex> lk(lock_of_handle(s->gpu_index));
     delete s;
 }
 
@@ -311,7 +313,7 @@ rdr_mesh_topology *rdr_mesh_topology_create(const int *indices, int num_triangle
 void rdr_mesh_topology_destroy(rdr_mesh_topology *topology) {
     if (!topology) return;
     rdr::vnrm::Topology *t = reinterpret_cast<rdr::vnrm::Topology *>(topology);
-    std::lock_guard<std::recursive_mutex> lk(device_lock(t->gpu_index));
+    std::lock_guard<std::recursive_mutex> lk(lock_of_handle(t->gpu_index));
     // best effort, not the guard: the plan is deleted also when its device cannot be selected any more, and there is nobody to
     // report that to
     try { exec::select_device(t->gpu_index >= 0, t->gpu_index); } catch (const std::exception &) {}
@@ -430,8 +432,8 @@ void rdr_trace_stats_get(rdr_trace_stats *out) {
 }
 
 uint64_t rdr_trim_cache(void) {
-    std::unique_lock<std::recursive_mutex> all[16];                 // every device, in index order (a call holds one lock only)
-    for (int d = 0; d < 16; ++d) all[d] = std::unique_lock<std::recursive_mutex>(g_device_lock[d]);
+    std::vector<std::unique_lock<std::recursive_mutex>> all;        // every device, in index order (a call holds one lock only)
+    for (std::recursive_mutex &m : g_device_lock) all.emplace_back(m);
     rdr::drop_edge_cache();            // the last Scene's edge structures, kept for the next one (scene.cpp: EdgeCache)
     const uint64_t bytes = exec::pool_cached_bytes();
     exec::pool_trim();

@@ -477,11 +477,15 @@ void delete_edge_data(EdgeData *e) {
 }
 
 EdgeData *compute_edge_data(const Scene &scene) {
-    // one build at a time PER DEVICE: the topology caches below are per device (like scene.cpp's edge / topology caches), and
-    // builds of different Scenes may be in flight together now that they run beside the caller (scene.cpp: create_scene)
-    const int dev_slot = (scene.gpu_index < 0 ? 0 : scene.gpu_index) & 15;
-    static std::mutex *build_locks = new std::mutex[16];
-    std::lock_guard<std::mutex> build_guard(build_locks[dev_slot]);
+    // one build at a time PER DEVICE: the topology caches are per device (like scene.cpp's edge / topology caches) and guarded by
+    // the build's lock; builds of different Scenes may be in flight together now that they run beside the caller (scene.cpp:
+    // create_scene).  Never destroyed: the edge-builder thread may be in here at exit.
+    struct MergedCache { std::vector<std::vector<int>> indices; std::vector<std::vector<EdgeD>> merged; };      // "edge list" below
+    struct GatherCache { std::vector<EdgeD> canon; rt::BvhHost bvh; };                                           // "billboard hierarchy" below
+    struct DeviceBuild { std::mutex lock; MergedCache merged; GatherCache gather; };
+    static auto *builds = new PerDevice<DeviceBuild>();
+    DeviceBuild &build = builds->at(scene.gpu_index);
+    std::lock_guard<std::mutex> build_guard(build.lock);
     PhaseTimer timer("edge build");
     std::unique_ptr<EdgeData> ed(new EdgeData());
     const int ns = (int)scene.shapes.size();
@@ -499,9 +503,7 @@ EdgeData *compute_edge_data(const Scene &scene) {
     // The first half of the construction -- half-edges sorted by vertex ids, runs merged into edges -- depends on the index
     // buffer only; a shape whose index buffer equals the one seen last at its position reuses it (an optimisation loop moves
     // vertices, not connectivity).  Everything after it depends on positions and is redone.
-    struct MergedCache { std::vector<std::vector<int>> indices; std::vector<std::vector<EdgeD>> merged; };
-    static MergedCache *merged_caches = new MergedCache[16];         // one build at a time per device (build_locks above; scene.cpp: EdgeBuilder)
-    MergedCache *merged_cache = merged_caches + dev_slot;
+    MergedCache *merged_cache = &build.merged;
     const bool cache_allowed = !(scene.build_flags & RDR_BUILD_NO_REFIT);
     if ((int)merged_cache->indices.size() != ns) { merged_cache->indices.assign(ns, {}); merged_cache->merged.assign(ns, {}); }
     std::vector<EdgeD> &edges = ed->edges;
@@ -654,9 +656,7 @@ EdgeData *compute_edge_data(const Scene &scene) {
         // of the previous one refits it -- whatever the motion did to the order of the list and to which coplanar edges
         // dropped out.  A canonical edge that is not in the current list keeps its place and its box (it is a real edge of
         // the mesh) but gets a leaf record no query accepts (GatherLeaf with an empty Hough interval).
-        struct GatherCache { std::vector<EdgeD> canon; rt::BvhHost bvh; };
-        static GatherCache *gather_caches = new GatherCache[16];         // one build at a time per device (build_locks above)
-        GatherCache *gather_cache = gather_caches + dev_slot;
+        GatherCache *gather_cache = &build.gather;
         rt::BvhHost gather_built;
         double &expand_out = ed->edge_bounds_expand;
         const bool gather_on_device = ed->device_trees && exec::kDeviceBvh;

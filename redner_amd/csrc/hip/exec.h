@@ -7,11 +7,12 @@
 //   * exec::launch      -- one lane per thread, 256-thread workgroups (4 wave64 per workgroup)
 //   * exec::DeviceBuf   -- HBM allocations through hipMalloc (no unified memory: the reference's
 //                          cudaMallocManaged scratch, src/buffer.h:53-56, page-faults per launch)
-//   * exec::compact / exec::trace_* -- hand-written kernels in compact.hip / trace.hip
+//   * exec::compact / exec::trace -- hand-written kernels (below / trace.hip); the device runtime they run on is runtime.hip
 // The only other implementation of this interface is the single-threaded debugging harness under
 // tests/hostsim/, which is test infrastructure and is never loaded by the product.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../per_device.h"
 #include <stdint.h>
 #include <stdio.h>
 #include <atomic>
@@ -219,7 +220,7 @@ inline void *dmalloc(size_t bytes) {
     return p;
 }
 inline void dfree(void *p) { if (p) (void)hipFree(p); }
-// Caching allocator behind every per-call buffer (trace.hip): blocks go back to a per-device free list instead of
+// Caching allocator behind every per-call buffer (runtime.hip): blocks go back to a per-device free list instead of
 // hipFree, so a render() / Scene of the same shape as an earlier one allocates nothing (hipMalloc + hipFree of the ~60
 // arrays of a 1024 x 1024 render cost milliseconds and hipFree synchronises the device).  pool_trim() releases the cache.
 void *pool_alloc(size_t bytes);
@@ -251,7 +252,7 @@ constexpr bool kDeviceEdgeTrees = true;         // the edge hierarchies are buil
 constexpr bool kDeviceBvh = true;               // ... and so is the triangle hierarchy (bvh_gpu.cpp)
 __host__ __device__ inline void gather_stats_add(long, long, int, int) {}      // a hook of the CPU debugging harness
 inline void device_sync() { (void)hipDeviceSynchronize(); }        // every stream of the device (error paths; never throws)
-// Batched transfers for the Scene build (trace.hip): every array goes through one pinned staging buffer, the copies are
+// Batched transfers for the Scene build (runtime.hip): every array goes through one pinned staging buffer, the copies are
 // queued on the stream and ONE synchronisation ends the batch -- a pageable hipMemcpy + sync per array cost 30-200 us each,
 // ~50 of them per Scene.
 void upload_async(void *dst, const void *src, size_t bytes);      // src may be reused as soon as this returns
@@ -266,7 +267,7 @@ inline int current_device() { int d = 0; (void)hipGetDevice(&d); return d; }
 // depth): each of them keeps a fraction of the lanes busy and waits on dependent loads, so they fill each other's gaps.
 // StreamScope redirects every launch made inside it; Fence orders two streams (record on the producer, gate the consumer).
 // (render.cpp: Fork puts the two together -- the one way the host driver puts work on a side stream.)
-hipStream_t side_stream(int k);          // trace.hip: two non-blocking streams per device, created on first use
+hipStream_t side_stream(int k);          // runtime.hip: two non-blocking streams per device, created on first use
 struct StreamScope {
     hipStream_t saved;
     explicit StreamScope(hipStream_t s) : saved(ctx().stream) { ctx().stream = s; }
@@ -280,18 +281,16 @@ constexpr int kMaxHelpers = 3;
 class SecondThread {
 public:
     static SecondThread &get(int k = 0) {                          // helper k OF THE CALLING THREAD'S DEVICE; never destroyed
+        struct Helpers { SecondThread *t[kMaxHelpers] = {}; };
         static std::mutex lock;
-        static SecondThread *t[16][kMaxHelpers] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
+        static rdr::PerDevice<Helpers> helpers;
         std::lock_guard<std::mutex> lk(lock);
-        SecondThread *&p = t[dev & 15][k];
+        SecondThread *&p = helpers.at(current_device()).t[k];
         if (!p) p = new SecondThread();
         return *p;
     }
     void start(std::function<void()> job) {
-        int dev = 0;
-        check(hipGetDevice(&dev), "hipGetDevice");
+        const int dev = current_device();
         std::unique_lock<std::mutex> lk(m_);
         cv_.wait(lk, [&] { return state_ == 0; });              // never overwrite a job that has not been taken / finished
         job_ = std::move(job); device_ = dev; state_ = 1;
@@ -305,14 +304,14 @@ public:
 private:
     SecondThread() { std::thread([this] { loop(); }).detach(); }
     void loop() {
-        hipStream_t streams[16] = {};
+        rdr::PerDevice<hipStream_t> streams;
         for (;;) {
             std::function<void()> job; int dev;
             { std::unique_lock<std::mutex> lk(m_); cv_.wait(lk, [&] { return state_ == 1; }); job = std::move(job_); dev = device_; state_ = 2; }
             std::exception_ptr failure;
             try {
                 check(hipSetDevice(dev), "hipSetDevice");
-                hipStream_t &s = streams[dev & 15];
+                hipStream_t &s = streams.slot[dev];       // the caller's device: it has passed SecondThread::get
                 if (!s) {
                     static const bool low = std::getenv("RDR_HELPER_LOW") != nullptr;        // experiment: helpers at the lowest priority
                     int least = 0, greatest = 0;
@@ -482,7 +481,7 @@ __global__ void __launch_bounds__(256, RDR_CHUNKED_MIN_BLOCKS) chunked_kernel(W 
         }
     }
 }
-int *persistent_counter();          // trace.hip: ring of zeroed ints, one per launch
+int *persistent_counter();          // runtime.hip: ring of zeroed ints, one per launch
 template <class W>
 inline void launch_chunked(Count n, const W &w, int items_per_lane = 4, int idle_min = 16, int steps = 8) {
     if (n.upper <= 0) return;
@@ -618,7 +617,7 @@ CompactScratch &compact_scratch(int nblocks, int which = 0);      // `which`: co
 // `out` must not alias `in`: a workgroup may scatter into a tile that an earlier-numbered workgroup has not read yet.
 // compact_dev: nothing comes back to the host.  The kept items go to out[*append_at ...] (append_at null: out[0 ...]) and
 // the returned Count says how many items `out` now holds (in device memory) and what the host can bound it by.
-int *new_count();                    // trace.hip: a device int from a per-thread ring, for one compaction's result
+int *new_count();                    // runtime.hip: a device int from a per-thread ring, for one compaction's result
 // `pos_out` (optional): pos_out[k] = position in the input list of the k-th kept item.
 template <class P>
 inline Count compact_dev(const int *in, Count n, int *out, const P &pred, const Count *append_at = nullptr, int *dyn = nullptr, int inc = 0,

@@ -187,15 +187,13 @@ struct EdgeCache {
     std::shared_future<std::shared_ptr<EdgeData>> result;
 };
 // (one per device: calls on one device are serialised by the API lock of that device, capi.cpp)
-static EdgeCache *edge_cache(int device) { static EdgeCache *c = new EdgeCache[16]; return c + ((device < 0 ? 0 : device) & 15); }
+static PerDevice<EdgeCache> &edge_caches() { static auto *c = new PerDevice<EdgeCache>(); return *c; }
 // The last triangle hierarchy that was BUILT (index buffers + the build): a Scene with the same connectivity refits a copy of it.
 struct TopologyCache { std::vector<std::vector<int>> indices; rt::BvhHost bvh; std::shared_ptr<rt::BvhDev> dev; int gpu_index = -1; };
-static TopologyCache *topology_cache(int device) { static TopologyCache *c = new TopologyCache[16]; return c + ((device < 0 ? 0 : device) & 15); }
-void drop_edge_cache() {
-    for (int d = 0; d < 16; ++d) {       // (rdr_trim_cache holds every device's lock)
-        *edge_cache(d) = EdgeCache();    // the device structures go when the last Scene that shares them does
-        *topology_cache(d) = TopologyCache();
-    }
+static PerDevice<TopologyCache> &topology_caches() { static auto *c = new PerDevice<TopologyCache>(); return *c; }
+void drop_edge_cache() {                 // (rdr_trim_cache holds every device's lock)
+    for (EdgeCache &c : edge_caches()) c = EdgeCache();       // the device structures go when the last Scene that shares them does
+    for (TopologyCache &c : topology_caches()) c = TopologyCache();
     drop_gather_cache();
 }
 
@@ -400,7 +398,7 @@ Scene *create_scene(const rdr_camera_desc *cam, const rdr_shape_desc *shapes, in
     // hierarchy (raytri.h), and it is rebuilt once its inner surface area has grown by more than 30 %.  RDR_BUILD_NO_REFIT: always build.
     // On the GPU build the hierarchy never exists on the host: bvh_gpu.cpp builds it from the caller's device arrays, or --
     // same connectivity as the last build -- refits a copy of that build's records (below, once the shape table is uploaded).
-    TopologyCache *topo_cache = topology_cache(gpu_index);           // guarded by the device's API lock (capi.cpp)
+    TopologyCache *topo_cache = &topology_caches().at(gpu_index);          // guarded by the device's API lock (capi.cpp)
     const bool refit_allowed = !(s.build_flags & RDR_BUILD_NO_REFIT);
     rt::BvhHost bvh_built;
     auto bvh_job = hostpool::run([&meshes, &bvh_built, &s, refit_allowed, topo_cache] {      // (joins in its destructor on an early exit)
@@ -493,7 +491,7 @@ Scene *create_scene(const rdr_camera_desc *cam, const rdr_shape_desc *shapes, in
         const bool sync_edges = (s.build_flags & RDR_BUILD_SYNC_EDGES) != 0;
         // Everything the edge structures are computed from (edges.cpp: compute_edge_data): if it equals what the previous
         // Scene's were computed from, that result -- finished or still in the builder's hands -- is this Scene's too.
-        EdgeCache *cache = edge_cache(gpu_index);             // guarded by the device's API lock (capi.cpp)
+        EdgeCache *cache = &edge_caches().at(gpu_index);           // guarded by the device's API lock (capi.cpp)
         const bool cache_allowed = !(s.build_flags & (RDR_BUILD_NO_EDGE_CACHE | RDR_BUILD_NO_REFIT));
         const bool hit = cache_allowed && cache->result.valid() && cache->gpu_index == s.gpu_index &&
                          cache->primary == s.use_primary_edges && cache->secondary == s.use_secondary_edges &&

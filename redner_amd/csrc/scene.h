@@ -12,6 +12,7 @@
 #include "bvh.h"
 #include "bvh_gpu.h"
 #include "scene_data.h"
+#include "per_device.h"
 #include <string>
 #include <vector>
 #include <future>

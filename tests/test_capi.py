@@ -125,3 +125,39 @@ def test_arena_rule(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert 'arena rule ok' in r.stdout
+
+
+def _device_index_beyond_the_table_is_an_error(lib):
+    """A device index the per-device tables (csrc/per_device.h) have no slot for is refused where it enters, with a text that names
+    the index and the limit -- it used to share device 0's lock, caches and pool lists; a call that succeeds clears the text.  No
+    kernel runs."""
+    assert not lib.rdr_mesh_topology_create(None, 0, 1, 1, 16)
+    text = lib.rdr_last_error().decode()
+    assert re.search(r'device index 16\b', text) and re.search(r'\b16 devices\b', text), text
+    out = (ctypes.c_int32 * 10)()
+    assert lib.rdr_debug_trace_plan(1000, 24, 1, 20, 1000, 0, 0, 0, None, out) == 0       # host arithmetic only
+    assert lib.rdr_last_error().decode() == ''
+
+
+def test_device_index_beyond_the_table_is_an_error_harness(hostsim_backend):
+    from redner_amd import _capi
+    _device_index_beyond_the_table_is_an_error(_capi.lib())
+
+
+@pytest.mark.gpu
+def test_device_index_beyond_the_table_is_an_error_product(gpu_backend):
+    from redner_amd import _capi
+    _device_index_beyond_the_table_is_an_error(_capi.lib())
+
+
+def test_per_device_rule(tmp_path):
+    """csrc/per_device.h (tests/per_device), as a program of its own under ASan + UBSan: sixteen distinct slots, host memory on
+    slot 0, an index beyond them is an error that names it, iteration in index order, slots of a type that is not copied."""
+    import subprocess
+    exe = str(tmp_path / 'per_device_rule')
+    subprocess.check_call(['g++', '-std=c++17', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
+                           '-I' + os.path.join(ROOT, 'redner_amd', 'csrc'),
+                           os.path.join(ROOT, 'tests', 'per_device', 'per_device_rule.cpp'), '-o', exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert 'per-device rule ok' in r.stdout

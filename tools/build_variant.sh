@@ -7,7 +7,7 @@ NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd); CSRC=$ROOT/redner_amd/csrc; OBJ=$ROOT/build/variant_$NAME
 mkdir -p $OBJ $ROOT/variants
 FLAGS="--offload-arch=gfx950 -std=c++17 -O3 -fPIC -I$CSRC/hip -I$CSRC -Wno-unused-result -pthread -ffp-contract=off $*"
-for f in capi.cpp scene.cpp render.cpp edges.cpp edges_gpu.cpp bvh_gpu.cpp hip/trace.hip; do
+for f in capi.cpp scene.cpp render.cpp edges.cpp edges_gpu.cpp bvh_gpu.cpp hip/runtime.hip hip/trace.hip; do
   /opt/rocm/bin/hipcc -x hip $FLAGS -c $CSRC/$f -o $OBJ/$(basename $f).o &
 done
 /opt/rocm/bin/hipcc $FLAGS -c $CSRC/bvh.cpp -o $OBJ/bvh.cpp.o &
