@@ -211,6 +211,11 @@ IMAGE_SIGNATURES = {
     'rdr_pyramid_loss': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _p, _p, _i64, _i]),
     'rdr_pyramid_loss_backward': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _i64, _p, _p, _p, _p, _i64, _i]),
 }
+# Every symbol of include/redner_amd_debug.h, the companion header of the test hooks that came after redner_amd.h was fixed: the same
+# form again (tests/test_lane_park.py compares this table with that header).
+DEBUG_SIGNATURES = {
+    'rdr_debug_lane_park': (_i, [_i, _p, _p, _p, _p]),
+}
 
 # rdr_scatter_op / rdr_scatter_target (rdr_debug_grad_scatter)
 SCATTER_ACCUM, SCATTER_ACCUM_TEXEL, SCATTER_ACCUM_PLAIN, SCATTER_ACCUM_TRIPLE, SCATTER_ACCUM_TEXEL_TRIPLE, \
@@ -233,10 +238,11 @@ def load(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % path)
     lib = C.CDLL(path)
-    for name in EXPORTS + tuple(MESH_SIGNATURES) + tuple(IMAGE_SIGNATURES):
+    for name in EXPORTS + tuple(MESH_SIGNATURES) + tuple(IMAGE_SIGNATURES) + tuple(DEBUG_SIGNATURES):
         if not hasattr(lib, name):
             raise RuntimeError("redner_amd: %s does not export %s" % (path, name))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items()) + \
+            list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib, _lib_path = lib, path

@@ -1,5 +1,6 @@
 // capi.cpp -- extern "C" entry points declared in include/redner_amd.h.
 #include "../../include/redner_amd.h"
+#include "../../include/redner_amd_debug.h"
 #include "render.h"
 #include "tuning.h"
 #include "trace_plan.h"
@@ -538,6 +539,16 @@ int rdr_debug_grad_scatter(const rdr_scene *scene, const rdr_dscene_desc *d_scen
         const rdr::Scene &s = *reinterpret_cast<const rdr::Scene *>(scene);
         OnDevice on(s);
         rdr::debug_grad_scatter(s, *d_scene, (size_t)job_samples, op, plain != 0, num_lanes, active, target, index, values);
+    });
+}
+
+/* Test hook: the lane park of the stage bodies alone (render.cpp: debug_lane_park). */
+int rdr_debug_lane_park(int num_lanes, const uint8_t *active, const double *in, double *out, int32_t *columns) {
+    return status([&] {
+        if (num_lanes < 0 || num_lanes > kDebugMaxItems) throw std::runtime_error("rdr_debug_lane_park: num_lanes out of range");
+        if (!columns || (num_lanes > 0 && (!active || !in || !out))) throw std::runtime_error("rdr_debug_lane_park: an array is missing");
+        OnDevice on(exec::current_device());
+        *columns = rdr::debug_lane_park(num_lanes, active, in, out);
     });
 }
 

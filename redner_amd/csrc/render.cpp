@@ -1287,6 +1287,58 @@ void debug_grad_scatter(const Scene &scene, const rdr_dscene_desc &ds, size_t jo
     exec::sync();                      // the probe and the fold have finished: `held` may go back to the pool
 }
 
+// ---- rdr_debug_lane_park (include/redner_amd.h): one stage whose active lanes park kMaxParkDoubles doubles and fetch them back ----
+namespace {
+struct LaneParkProbe {
+    const unsigned char *active; const double *in; double *out;
+    RDR_FN void operator()(int i) const {
+        if (!active[i]) return;        // before the park is declared: how the lanes of the stages with nothing to do leave
+        constexpr int K = kMaxParkDoubles;
+        static_assert(K >= 22, "the probe's layout: two groups of double, V3, V2, double[4] and a V2");
+        const double *x = in + (size_t)K * i;
+        double *y = out + (size_t)K * i;
+        RDR_PARK_DECL(park, K);
+        for (int b = 0; b < 20; b += 10) {
+            const double four[4] = {x[b + 6], x[b + 7], x[b + 8], x[b + 9]};
+            park.put(b, x[b]); park.put3(b + 1, v3(x[b + 1], x[b + 2], x[b + 3])); park.put2(b + 4, v2(x[b + 4], x[b + 5]));
+            park.put(b + 6, four);
+        }
+        park.put2(20, v2(x[20], x[21]));
+        for (int k = 22; k < K; ++k) park.put(k, x[k]);
+        // the second group takes half of itself on top (x + x / 2: one rounding, the same on every machine)
+        park.add(10, 0.5 * x[10]); park.add3(11, 0.5 * v3(x[11], x[12], x[13])); park.add2(14, 0.5 * v2(x[14], x[15]));
+        // ... and back, last column first
+        for (int k = K - 1; k >= 22; --k) y[k] = park.get(k);
+        const V2 tail = park.get2<V2>(20);
+        y[20] = tail.x; y[21] = tail.y;
+        for (int b = 10; b >= 0; b -= 10) {
+            double four[4];
+            park.get(b + 6, four);
+            const V2 two = park.get2<V2>(b + 4);
+            const V3 three = park.get3<V3>(b + 1);
+            y[b + 9] = four[3]; y[b + 8] = four[2]; y[b + 7] = four[1]; y[b + 6] = four[0];
+            y[b + 5] = two.y; y[b + 4] = two.x;
+            y[b + 3] = three.z; y[b + 2] = three.y; y[b + 1] = three.x;
+            y[b] = park.get(b);
+        }
+    }
+};
+}
+
+int debug_lane_park(int num_lanes, const uint8_t *active, const double *in, double *out) {
+    if (num_lanes <= 0) return kMaxParkDoubles;
+    const size_t n = (size_t)num_lanes, count = n * kMaxParkDoubles;
+    Arena held;
+    const unsigned char *d_active = held.put(active, n);
+    const double *d_in = held.put(in, count);
+    double *d_out = held.put(out, count);          // what the caller handed over stays where no lane writes
+    exec::upload_flush();
+    exec::launch(exec::Count(num_lanes), LaneParkProbe{d_active, d_in, d_out});
+    exec::download(out, d_out, sizeof(double) * count);
+    exec::sync();                      // the probe has finished: `held` may go back to the pool
+    return kMaxParkDoubles;
+}
+
 } // namespace rdr
 
 // Which transcendental functions this build of the stage kernels calls (include/redner_amd.h: rdr_libm_exact)

@@ -88,7 +88,15 @@ struct AdjBounceScatter {
 #ifndef RDR_ADJ_SCATTER_LEAN_BLOCKS          // (variant builds: tools/build_render_variant.sh x -DRDR_ADJ_SCATTER_LEAN_BLOCKS=4)
 #define RDR_ADJ_SCATTER_LEAN_BLOCKS 3
 #endif
-    static constexpr int kLeanBlocksPerCU = RDR_ADJ_SCATTER_LEAN_BLOCKS;         // 190 -> 168 registers (100 B of scratch), three waves per SIMD: +2 % on the benchmark
+    static constexpr int kLeanBlocksPerCU = RDR_ADJ_SCATTER_LEAN_BLOCKS;         // 182 -> 168 registers (52 B of scratch), three waves per SIMD: +2 % on the benchmark
+    // With the hit triangle parked through the surface adjoint the lean form fits three waves per SIMD without scratch (166
+    // registers), but alone that moved the benchmark by +0.2 ... +0.4 %, inside the run-to-run spread: not shipped
+    // (profiles/lane_park_notes.md).
+#ifndef RDR_PARK_ADJ_SCATTER                 // (variant builds: -DRDR_PARK_ADJ_SCATTER=1)
+#define RDR_PARK_ADJ_SCATTER 0
+#endif
+    static constexpr int kParkDoubles = kSurfParkDoubles + 4;      // 44 KiB of LDS per workgroup: three workgroups per CU
+    static_assert(kParkDoubles <= kMaxParkDoubles, "kMaxParkDoubles must cover every stage");
     RDR_FN void make_lean() { lean_scene(a.sc); lean_slice(a.v); lean_slice(a.vn); a.nd = 3; a.radiance_dim = 0; a.adj.plain = 1; }
     RDR_FN void make_mid() { mid_scene(a.sc); a.nd = 3; a.radiance_dim = 0; }
     RDR_FN void operator()(int idx) const {
@@ -191,7 +199,16 @@ struct AdjBounceScatter {
             DRay r_bar = dray_zero();
             RayDiff rd_bar = raydiff_zero();
             Ray br = make_ray(pos, wo);
+#if RDR_PARK_ADJ_SCATTER
+            // the hit triangle's corners and normals wait in the lane's LDS columns through the middle of the surface adjoint,
+            // and so does what this stage needs after it
+            RDR_PARK_DECL(park, kParkDoubles);
+            park.put3(kSurfParkDoubles, dir_bar); park.put(kSurfParkDoubles + 3, c.mrough);
+            adj_surf_at(bsh, btri, br, load_rdiff(vn, p), bp_bar, raydiff_zero(), r_bar, rd_bar, tg, !sc.no_diffs, sc.plain_materials != 0, park);
+            dir_bar = park.get3<V3>(kSurfParkDoubles); c.mrough = park.get(kSurfParkDoubles + 3);
+#else
             adj_surf_at(bsh, btri, br, load_rdiff(vn, p), bp_bar, raydiff_zero(), r_bar, rd_bar, tg, !sc.no_diffs, sc.plain_materials != 0);
+#endif
             tg_shape = bshape; tg_tri = btri;
             if (c.mrough > 0.01f) {
                 pos_bar -= dir_bar;
@@ -225,9 +242,14 @@ struct AdjBounceNee {
     // launch on the config-5 stand-in); the same cap costs AdjBounceScatter 650 B of spills and 1.8 -> 3.0 ms, so it keeps one wave
     static constexpr int kMinBlocksPerCU = 2;
     static constexpr int kMidBlocksPerCU = 2;
-#ifdef RDR_ADJ_NEE_LEAN_BLOCKS              // (variant builds only; the lean form runs at 231 registers, two waves per SIMD)
+#ifdef RDR_ADJ_NEE_LEAN_BLOCKS              // (variant builds only; the lean form needs 156 registers with the lane park below -- three waves per SIMD -- and 208 without)
     static constexpr int kLeanBlocksPerCU = RDR_ADJ_NEE_LEAN_BLOCKS;
 #endif
+#ifndef RDR_PARK_ADJ_NEE                     // (variant builds: -DRDR_PARK_ADJ_NEE=0 keeps everything in registers)
+#define RDR_PARK_ADJ_NEE 1
+#endif
+    static constexpr int kParkDoubles = 22;        // 44 KiB of LDS per workgroup: three workgroups per CU
+    static_assert(kParkDoubles <= kMaxParkDoubles, "kMaxParkDoubles must cover every stage");
     AdjBounceArgs a;
     RDR_FN void make_lean() { lean_scene(a.sc); lean_slice(a.v); lean_slice(a.vn); a.nd = 3; a.radiance_dim = 0; a.adj.plain = 1; }
     RDR_FN void make_mid() { mid_scene(a.sc); a.nd = 3; a.radiance_dim = 0; }
@@ -317,7 +339,19 @@ struct AdjBounceNee {
         Surf lp_bar = surf_zero();
         lp_bar.geom_normal = cl_bar * wo;
         V3 wi_bar = v3(0);
+#if RDR_PARK_ADJ_NEE
+        // what the BSDF's adjoint neither reads nor writes waits in the lane's LDS columns while it runs (22 doubles)
+        RDR_PARK_DECL(park, kParkDoubles);
+        park.put3(0, lv_bar[0]); park.put3(3, lv_bar[1]); park.put3(6, lv_bar[2]);
+        park.put3(9, thr_bar); park.put3(12, dir); park.put(15, d2); park.put(16, d2_bar);
+        park.put3(17, lp_bar.geom_normal); park.put2(20, ld.uv);
+#endif
         adj_bsdf_eval(*c.mat, c.sp, c.wi, wo, c.mrough, f_bar, gm, sp_bar, wi_bar, wo_bar);
+#if RDR_PARK_ADJ_NEE
+        lv_bar[0] = park.get3<V3>(0); lv_bar[1] = park.get3<V3>(3); lv_bar[2] = park.get3<V3>(6);
+        thr_bar = park.get3<V3>(9); dir = park.get3<V3>(12); d2 = park.get(15); d2_bar = park.get(16);
+        lp_bar.geom_normal = park.get3<V3>(17); ld.uv = park.get2<V2>(20);
+#endif
         V3 dir_bar = wo_bar / sqrt(d2);
         double sd_bar = -sum(wo_bar * dir) / d2;
         d2_bar += (0.5f * sd_bar / sqrt(d2));
@@ -379,6 +413,13 @@ RDR_FN void adj_first_hit_channels(const SceneD &sc, const GScene &g, const Chan
 struct AdjPrimary {
     static constexpr int kMinBlocksPerCU = 2;
     static constexpr int kMidBlocksPerCU = 2;
+    // The lean form reaches three waves per SIMD with the first-hit triangle and its gradient parked (210 -> 160 registers), but the
+    // general form then spills 8 bytes more than without (456 -> 464): not shipped (profiles/lane_park_notes.md).
+#ifndef RDR_PARK_ADJ_PRIMARY                 // (variant builds: -DRDR_PARK_ADJ_PRIMARY=1)
+#define RDR_PARK_ADJ_PRIMARY 0
+#endif
+    static constexpr int kParkDoubles = kSurfParkDoubles;        // 36 KiB of LDS per workgroup
+    static_assert(kParkDoubles <= kMaxParkDoubles, "kMaxParkDoubles must cover every stage");
     SceneD sc; GScene g; SamplerD rng; int sample_center;
     VSlice v0; const float *d_image; int nd, radiance_dim; double weight;
     AdjState adj; float *screen_grad; ChannelsD ch;
@@ -387,10 +428,19 @@ struct AdjPrimary {
     RDR_FN void operator()(int p) const {
         TriGrad tg = trigrad_zero();          // gradient of the first-hit triangle, scattered by the whole wave at the end
         int tg_shape = -1, tg_tri = -1;
-        RDR_INLINE_CALL camera_vertex(p, tg, tg_shape, tg_tri);
+#if RDR_PARK_ADJ_PRIMARY
+        RDR_PARK_DECL(park, kParkDoubles);
+        RDR_INLINE_CALL camera_vertex(p, tg, tg_shape, tg_tri, park);
+        if (tg_shape >= 0) {               // positions and normals of the triangle's gradient waited in LDS while the camera's was formed
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { tg.p[k] = park.get3<V3>(3 * k); tg.n[k] = park.get3<V3>(9 + 3 * k); }
+        }
+#else
+        RDR_INLINE_CALL camera_vertex(p, tg, tg_shape, tg_tri, KeepInRegisters());
+#endif
         scatter_trigrad_wave(sc.shapes, g.shapes, tg_shape, tg_tri, tg, sc.plain_materials != 0);
     }
-    RDR_FN void camera_vertex(int p, TriGrad &tg, int &tg_shape, int &tg_tri) const {
+    template <class Park> RDR_FN void camera_vertex(int p, TriGrad &tg, int &tg_shape, int &tg_tri, const Park &park) const {
         int shape = v0.shape[p];
         Ray ray = load_ray(v0, p);
         RayDiff rd = load_rdiff(v0, p);
@@ -432,7 +482,11 @@ struct AdjPrimary {
                 Surf sp = surf_at(sc.shapes[shape], v0.tri[p], ray, rd, tmp, !sc.no_diffs);
                 adj_first_hit_channels(sc, g, ch, d_image, weight, p, shape, sp, ray, pt_bar, r_bar.org);
             }
-            adj_surf_at(sc.shapes[shape], v0.tri[p], ray, rd, pt_bar, raydiff_zero(), r_bar, prd_bar, tg, !sc.no_diffs, sc.plain_materials != 0);
+            // the first-hit triangle's corners and normals wait in the lane's LDS columns through the middle of the surface adjoint,
+            // then the positions and normals of its gradient do until the stage scatters them
+            adj_surf_at(sc.shapes[shape], v0.tri[p], ray, rd, pt_bar, raydiff_zero(), r_bar, prd_bar, tg, !sc.no_diffs, sc.plain_materials != 0, park);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { park.put3(3 * k, tg.p[k]); park.put3(9 + 3 * k, tg.n[k]); }
             tg_shape = shape; tg_tri = v0.tri[p];
         }
         V2 s = v2(0.5, 0.5);

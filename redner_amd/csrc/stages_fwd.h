@@ -164,6 +164,9 @@ template <class Walk> struct MidWalk {
     RDR_DEV_FN bool gate_closed() const { return w.gate_closed(); }
 };
 
+// The widest lane park (lane_park.h: RDR_PARK_DECL) a stage declares; rdr_debug_lane_park exercises this many columns.
+constexpr int kMaxParkDoubles = 22;
+
 struct LightDraw { double light_sel, tri_sel; V2 uv; };
 RDR_FN LightDraw draw_light(const SamplerD &rng, const SamplerD::Lane &ln, int dim) {
     return LightDraw{rng.draw(ln, dim), rng.draw(ln, dim + 1), v2(rng.draw(ln, dim + 2), rng.draw(ln, dim + 3))};
@@ -439,19 +442,10 @@ struct BounceSample {
     }
 };
 
-// Result of evaluating one bounce (shared by the forward and the adjoint stage).
-struct BounceEval {
-    V3 nee, scatter;        // contributions before multiplying the throughput
-    V3 next_thr; bool next_thr_valid;
-};
-
-// NEE + BSDF-hit emission with power-2 MIS (src/path_contribution.cpp:24-118).
-RDR_FN BounceEval eval_bounce(const SceneD &sc, const VertexCtx &c, V3 thr,
-                              bool nee_visible, const LightPick &pk, const Surf &lp, V2 light_uv,
-                              int bshape, const Surf &bp, V3 bsdf_dir) {
-    BounceEval r;
-    r.nee = r.scatter = r.next_thr = v3(0);
-    r.next_thr_valid = false;
+// NEE + BSDF-hit emission with power-2 MIS (src/path_contribution.cpp:24-118), in two halves so that a stage can put what
+// only the other half needs aside in between (BounceContrib parks it in LDS): next-event estimation ...
+RDR_FN V3 eval_bounce_nee(const SceneD &sc, const VertexCtx &c, bool nee_visible, const LightPick &pk, const Surf &lp, V2 light_uv) {
+    V3 nee = v3(0);
     V3 pos = c.sp.position;
     if (nee_visible && pk.shape_id >= 0) {
         const ShapeD &lsh = sc.shapes[pk.shape_id];
@@ -466,7 +460,7 @@ RDR_FN BounceEval eval_bounce(const SceneD &sc, const VertexCtx &c, V3 thr,
                 double pdf_nee = sc.light_pmf[lsh.light_id] / sc.light_areas[lsh.light_id];
                 double pdf_b = bsdf_pdf(*c.mat, c.sp, c.wi, wo, c.mrough) * g;
                 double mis = 1 / (1 + sq(pdf_b / pdf_nee));
-                r.nee = (mis * g / pdf_nee) * f * v3f(l.intensity);
+                nee = (mis * g / pdf_nee) * f * v3f(l.intensity);
             }
         }
     } else if (nee_visible && sc.envmap != nullptr) {
@@ -478,9 +472,19 @@ RDR_FN BounceEval eval_bounce(const SceneD &sc, const VertexCtx &c, V3 thr,
             V3 Le = envmap_eval(*sc.envmap, wo, raydiff_zero());
             double pdf_b = bsdf_pdf(*c.mat, c.sp, c.wi, wo, c.mrough);
             double mis = 1 / (1 + sq(pdf_b / pdf_nee));
-            r.nee = (mis / pdf_nee) * f * Le;
+            nee = (mis / pdf_nee) * f * Le;
         }
     }
+    return nee;
+}
+// ... and the BSDF-sampled continuation: `scatter` and the factor f / pdf the throughput is multiplied by on the way to the
+// next vertex (`carries` false: the direction carries nothing, the next throughput is zero); both before multiplying the throughput
+struct ScatterEval { V3 scatter, thr_factor; bool next_thr_valid, carries; };
+RDR_FN ScatterEval eval_bounce_scatter(const SceneD &sc, const VertexCtx &c, int bshape, const Surf &bp, V3 bsdf_dir) {
+    ScatterEval r;
+    r.scatter = r.thr_factor = v3(0);
+    r.next_thr_valid = r.carries = false;
+    V3 pos = c.sp.position;
     if (bshape >= 0) {
         const ShapeD &bsh = sc.shapes[bshape];
         V3 dir = bp.position - pos;
@@ -500,9 +504,8 @@ RDR_FN BounceEval eval_bounce(const SceneD &sc, const VertexCtx &c, V3 thr,
                     r.scatter = (mis / pdf_b) * f * v3f(l.intensity);
                 }
             }
-            r.next_thr = thr * (f / pdf_b);
-        } else {
-            r.next_thr = v3(0);
+            r.thr_factor = f / pdf_b;
+            r.carries = true;
         }
     } else if (sc.envmap != nullptr) {
         // the BSDF-sampled ray left the scene: it sees the environment light (:99-118)
@@ -518,7 +521,6 @@ RDR_FN BounceEval eval_bounce(const SceneD &sc, const VertexCtx &c, V3 thr,
     }
     return r;
 }
-
 // Next-event estimation towards an area light: is this vertex / light-sample pair one of the cases in which the estimator AND
 // every adjoint of it are exactly zero for geometric reasons -- the light faces away, the sample lies below the horizon of the
 // shading or the geometric normal (bsdf_eval's early-outs)?  ONE definition, used by BounceContrib (it folds the answer into
@@ -546,6 +548,21 @@ RDR_FN bool nee_is_geometrically_zero(const SceneD &sc, const VertexCtx &c, cons
 struct BounceContrib {
     static constexpr int kMidBlocksPerCU = 3;
     static constexpr int kMinBlocksPerCU = 3;          // general form
+#ifndef RDR_PARK_BOUNCE_CONTRIB              // (variant builds: -DRDR_PARK_BOUNCE_CONTRIB=0 keeps everything in registers)
+#define RDR_PARK_BOUNCE_CONTRIB 1
+#endif
+#if RDR_PARK_BOUNCE_CONTRIB
+#ifndef RDR_BOUNCE_CONTRIB_LEAN_BLOCKS
+#ifdef RDR_PLATFORM_LIBM
+#define RDR_BOUNCE_CONTRIB_LEAN_BLOCKS 4
+#else           // the glibc-exact routines (libm_exact.h) need two registers more: 130, which a cap at 128 would spill (32 B)
+#define RDR_BOUNCE_CONTRIB_LEAN_BLOCKS 3
+#endif
+#endif
+    static constexpr int kLeanBlocksPerCU = RDR_BOUNCE_CONTRIB_LEAN_BLOCKS;      // 127 registers with the park (158 without): four waves per SIMD; exact build 130 (152): three
+#endif
+    static constexpr int kParkDoubles = 12;        // 24 KiB of LDS per workgroup
+    static_assert(kParkDoubles <= kMaxParkDoubles, "kMaxParkDoubles must cover every stage");
     SceneD sc; SamplerD rng; int dim, rng_shift;
     const int *active; VSlice v, vn;
     const rt::HitRec *h_nee, *h_bsdf;
@@ -591,9 +608,24 @@ struct BounceContrib {
         // (the camera paths of a gradient render feed no image and no edge estimate: their next-event term is consumed by nobody
         //  -- the adjoint stages re-evaluate it -- and is not evaluated; throughput and occlusion byte are what they leave behind)
         const bool consumed = sink.image != nullptr || sink.edge_contrib != nullptr;
-        BounceEval e = eval_bounce(sc, c, thr, !blocked && consumed, pk, lp, ld.uv, hb.shape, bp, load_ray(vn, p).dir);
-        if (e.next_thr_valid) st3(vn.thr, vn.n, p, 0, e.next_thr);
-        V3 pc = thr * (e.nee + e.scatter);
+#if RDR_PARK_BOUNCE_CONTRIB
+        // the continuation's hit point and the throughput wait in the lane's LDS columns while the next-event half runs, the
+        // next-event term and the throughput while the continuation half does
+        RDR_PARK_DECL(park, kParkDoubles);
+        park.put3(0, thr); park.put3(3, bp.position); park.put3(6, bp.frame.n); park.put3(9, bp.geom_normal);
+        V3 nee = eval_bounce_nee(sc, c, !blocked && consumed, pk, lp, ld.uv);
+        bp.position = park.get3<V3>(3); bp.frame.n = park.get3<V3>(6); bp.geom_normal = park.get3<V3>(9);
+        park.put3(3, nee);
+        const ScatterEval e = eval_bounce_scatter(sc, c, hb.shape, bp, load_ray(vn, p).dir);
+        const V3 thr_in = park.get3<V3>(0);
+        nee = park.get3<V3>(3);
+#else
+        const V3 nee = eval_bounce_nee(sc, c, !blocked && consumed, pk, lp, ld.uv);
+        const ScatterEval e = eval_bounce_scatter(sc, c, hb.shape, bp, load_ray(vn, p).dir);
+        const V3 thr_in = thr;
+#endif
+        if (e.next_thr_valid) st3(vn.thr, vn.n, p, 0, e.carries ? thr_in * e.thr_factor : v3(0));
+        V3 pc = thr_in * (nee + e.scatter);
         if (sink.image) {
             float *px = sink.image + (size_t)sink.nd * p + sink.radiance_dim;
             px[0] += float(sink.weight * pc.x); px[1] += float(sink.weight * pc.y); px[2] += float(sink.weight * pc.z);

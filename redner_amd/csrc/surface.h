@@ -314,9 +314,18 @@ RDR_FN TriGrad trigrad_zero() {
     return g;
 }
 
+// adj_surf_at needs the triangle's corners and vertex normals (18 doubles) at both ends of its body and not in the middle, where
+// its register peak lies.  A stage that hands it a lane park (lane_park.h: RDR_PARK_DECL, >= kSurfParkDoubles columns; the function
+// uses columns 0 .. 17) has them wait in LDS meanwhile; by default they stay where they are.
+constexpr int kSurfParkDoubles = 18;
+struct KeepInRegisters {
+    template <class V> RDR_FN void put3(int, const V &) const {}
+    template <class V> RDR_FN V get3(int, const V &v) const { return v; }
+};
+template <class Park = KeepInRegisters>
 RDR_FN void adj_surf_at(const ShapeD &sh, int tri, const Ray &ray, const RayDiff &rd,
                         const Surf &sp_bar, const RayDiff &new_rd_bar,
-                        DRay &ray_bar, RayDiff &rd_bar, TriGrad &g, bool diffs = true, bool plain = false) {
+                        DRay &ray_bar, RayDiff &rd_bar, TriGrad &g, bool diffs = true, bool plain = false, const Park &park = Park()) {
     // plain: no texture coordinate or vertex colour can carry an adjoint (constant materials, no vertex colours)
     RDR_CONTRACT_FAST
     TriVerts tv = load_tri(sh, tri);
@@ -335,6 +344,7 @@ RDR_FN void adj_surf_at(const ShapeD &sh, int tri, const Ray &ray, const RayDiff
         V3 p02 = tv.p0 - tv.p2, p12 = tv.p1 - tv.p2;
         dpdu = (uv12.y * p02 - uv02.y * p12) * inv;
     }
+    park.put3(0, tv.p0); park.put3(3, tv.p1); park.put3(6, tv.p2);
     V3 sn = gn;
     bool flipped = false;
     V3 n0 = v3(0), n1 = v3(0), n2 = v3(0), nn = v3(0), dnn_dx = v3(0), dnn_dy = v3(0);
@@ -352,6 +362,7 @@ RDR_FN void adj_surf_at(const ShapeD &sh, int tri, const Ray &ray, const RayDiff
         }
         sn = normalize(nn);
         if (dot(gn, sn) < 0.f) { gn = -gn; flipped = true; }
+        park.put3(9, n0); park.put3(12, n1); park.put3(15, n2);
     }
     V3 fx0 = normalize(dpdu);
     V3 fy0 = cross(sn, fx0);
@@ -384,6 +395,7 @@ RDR_FN void adj_surf_at(const ShapeD &sh, int tri, const Ray &ray, const RayDiff
     V2 udxy_bar = v2(0, 0), vdxy_bar = v2(0, 0);
     V3 p0_bar = v3(0), p1_bar = v3(0), p2_bar = v3(0);
     if (sh.normals) {
+        n0 = park.get3(9, n0); n1 = park.get3(12, n1); n2 = park.get3(15, n2);
         if (flipped) gn_bar = -gn_bar;
         // the reference additionally pushes the frame tangents through an onb() adjoint here
         adj_onb(sn, sp_bar.frame.x, sp_bar.frame.y, sn_bar);
@@ -434,6 +446,7 @@ RDR_FN void adj_surf_at(const ShapeD &sh, int tri, const Ray &ray, const RayDiff
         t_bar += sum(dpdy_bar * rd.dir_dy);
     }
 
+    tv.p0 = park.get3(0, tv.p0); tv.p1 = park.get3(3, tv.p1); tv.p2 = park.get3(6, tv.p2);
     V2 uv0_bar = v2(0, 0), uv1_bar = v2(0, 0), uv2_bar = v2(0, 0);
     if (uv_det == 0) {
         adj_onb(gn, dpdu_bar, v3(0), gn_bar);

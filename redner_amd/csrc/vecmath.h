@@ -10,6 +10,7 @@
 // (csrc/hip/exec.h).
 #pragma once
 #include "exec.h"   // resolved by include path: csrc/hip/exec.h for the gfx950 build
+#include "lane_park.h"
 #include <math.h>
 #include <stdint.h>
 
