@@ -16,6 +16,10 @@
     redner_amd.loss              gaussian_pyramid_loss, the image pyramid loss of the reference's optimisation scripts, on the
                                  native pyramid-loss kernels (an image gradient included):
                                  `from redner_amd import gaussian_pyramid_loss, GaussianPyramidLoss`
+    redner_amd.transform         gen_rotate_matrix and pose_vertices, the rigid pose of the reference's pose-estimation scripts
+                                 (rotate every vertex set about a centre, translate), on the native pose kernels, with
+                                 gradients to angles, translation, centre and vertices:
+                                 `from redner_amd import gen_rotate_matrix, pose_vertices, RotateMatrix, PoseVertices`
     redner_amd.install()         register redner_amd.redner as `redner` for the reference's
                                  unmodified pyredner package
 """
@@ -26,6 +30,7 @@ _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLigh
 _TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid', 'envmap_sampling_tables')
 _UTILS = ('SH_reconstruct', 'SHReconstruct')
 _LOSS = ('gaussian_pyramid_loss', 'GaussianPyramidLoss')
+_TRANSFORM = ('gen_rotate_matrix', 'pose_vertices', 'RotateMatrix', 'PoseVertices')
 _SHAPE = ('compute_vertex_normal', 'MeshTopology', 'VertexNormals', 'smooth', 'mesh_laplacian', 'bound_vertices', 'MeshLaplacian')
 
 
@@ -46,6 +51,9 @@ def __getattr__(name):
     if name in _LOSS:
         from . import loss
         return getattr(loss, name)
+    if name in _TRANSFORM:
+        from . import transform
+        return getattr(transform, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/redner_amd.h and its companion include/redner_amd_mesh.h.
+"""ctypes binding of the C ABI in include/redner_amd.h and its companion headers (redner_amd_mesh.h, _image.h, _pose.h, _debug.h).
 
 The shared library is the product: `redner_amd/lib/libredner_amd.so`, built by
 `__graft_entry__.build()` (hipcc, gfx950).  If it is missing the import fails loudly -- there is
@@ -211,6 +211,16 @@ IMAGE_SIGNATURES = {
     'rdr_pyramid_loss': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _p, _p, _i64, _i]),
     'rdr_pyramid_loss_backward': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _i64, _p, _p, _p, _p, _i64, _i]),
 }
+# Every symbol of include/redner_amd_pose.h, the third companion header (the rigid pose, csrc/pose.h): the same form again
+# (tests/test_pose.py compares this table with that header).
+POSE_SIGNATURES = {
+    'rdr_pose_scratch': (_i, [_i, c_int_p, C.POINTER(_i64), C.POINTER(_i64)]),
+    'rdr_pose_plan': (_i, [_i, c_int_p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    'rdr_rotate_matrix': (_i, [_p, _p, _i]),
+    'rdr_rotate_matrix_backward': (_i, [_p, _p, _p, _i]),
+    'rdr_pose_vertices': (_i, [_i, C.POINTER(_p), c_int_p, _p, _p, _p, C.POINTER(_p), _p, _p, _i64, _i]),
+    'rdr_pose_vertices_backward': (_i, [_i, C.POINTER(_p), c_int_p, _p, _p, _i, C.POINTER(_p), C.POINTER(_p), _p, _p, _p, _p, _i64, _i]),
+}
 # Every symbol of include/redner_amd_debug.h, the companion header of the test hooks that came after redner_amd.h was fixed: the same
 # form again (tests/test_lane_park.py compares this table with that header).
 DEBUG_SIGNATURES = {
@@ -238,11 +248,11 @@ def load(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % path)
     lib = C.CDLL(path)
-    for name in EXPORTS + tuple(MESH_SIGNATURES) + tuple(IMAGE_SIGNATURES) + tuple(DEBUG_SIGNATURES):
+    for name in EXPORTS + tuple(MESH_SIGNATURES) + tuple(IMAGE_SIGNATURES) + tuple(POSE_SIGNATURES) + tuple(DEBUG_SIGNATURES):
         if not hasattr(lib, name):
             raise RuntimeError("redner_amd: %s does not export %s" % (path, name))
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items()) + \
-            list(DEBUG_SIGNATURES.items()):
+            list(POSE_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib, _lib_path = lib, path

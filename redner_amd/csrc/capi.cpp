@@ -11,6 +11,7 @@
 #include "mesh_smooth.h"
 #include "sh_envmap.h"
 #include "pyramid_loss.h"
+#include "pose.h"
 #include <cstdio>
 #include "scene.h"
 #include <cstring>
@@ -299,6 +300,58 @@ int rdr_pyramid_loss_backward(const float *image, const float *target, int batch
         OnDevice on(gpu_index, "rdr_pyramid_loss_backward");
         const rdr::pyl::Plan p = rdr::pyl::make_plan(batch, height, width, channels, num_levels, weights, clamp, "rdr_pyramid_loss_backward");
         rdr::pyl::backward(p, image, target, saved, floats(saved_floats), upstream, d_image, d_target, scratch, floats(scratch_floats));
+    });
+}
+
+// ---- the rigid pose (csrc/pose.h, include/redner_amd_pose.h) ----
+int rdr_pose_scratch(int num_sets, const int *counts, int64_t *forward_floats, int64_t *backward_floats) {
+    return status([&] {
+        const rdr::pose::Table tb = rdr::pose::make_table(num_sets, counts, "rdr_pose_scratch");
+        if (forward_floats) *forward_floats = (int64_t)rdr::pose::forward_floats(tb);
+        if (backward_floats) *backward_floats = (int64_t)rdr::pose::backward_floats(tb);
+    });
+}
+
+int rdr_pose_plan(int num_sets, const int *counts, int *chunk_vertices, int *max_workgroups, int *workgroups) {
+    return status([&] {
+        const rdr::pose::Table tb = rdr::pose::make_table(num_sets, counts, "rdr_pose_plan");
+        if (chunk_vertices) *chunk_vertices = rdr::pose::kChunk;
+        if (max_workgroups) *max_workgroups = rdr::pose::kMaxGroups;
+        if (workgroups) *workgroups = tb.groups;
+    });
+}
+
+int rdr_rotate_matrix(const float *angles, float *matrix, int gpu_index) {
+    return status([&] {
+        OnDevice on(gpu_index, "rdr_rotate_matrix");
+        rdr::pose::rotate_matrix(angles, matrix);
+    });
+}
+
+int rdr_rotate_matrix_backward(const float *angles, const float *d_matrix, float *d_angles, int gpu_index) {
+    return status([&] {
+        OnDevice on(gpu_index, "rdr_rotate_matrix_backward");
+        rdr::pose::rotate_matrix_backward(angles, d_matrix, d_angles);
+    });
+}
+
+int rdr_pose_vertices(int num_sets, const float *const *vertices, const int *counts, const float *angles, const float *translation,
+                      const float *center, float *const *out, float *saved, float *scratch, int64_t scratch_floats, int gpu_index) {
+    return status([&] {
+        OnDevice on(gpu_index, "rdr_pose_vertices");
+        const rdr::pose::Table tb = rdr::pose::make_table(num_sets, counts, "rdr_pose_vertices");
+        rdr::pose::forward(tb, vertices, angles, translation, center, out, saved, scratch, floats(scratch_floats));
+    });
+}
+
+int rdr_pose_vertices_backward(int num_sets, const float *const *vertices, const int *counts, const float *angles, const float *saved,
+                               int own_center, const float *const *d_out, float *const *d_vertices, float *d_angles,
+                               float *d_translation, float *d_center, float *scratch, int64_t scratch_floats, int gpu_index) {
+    return status([&] {
+        OnDevice on(gpu_index, "rdr_pose_vertices_backward");
+        const rdr::pose::Table tb = rdr::pose::make_table(num_sets, counts, "rdr_pose_vertices_backward");
+        rdr::pose::backward(tb, vertices, angles, saved, own_center != 0, d_out, d_vertices, d_angles, d_translation, d_center, scratch,
+                            floats(scratch_floats));
     });
 }
 

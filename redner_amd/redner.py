@@ -544,6 +544,70 @@ def pyramid_loss_backward(image, target, saved, saved_floats, upstream, d_image,
           _addr(scratch) or None, int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
+def _count_table(counts):
+    return (C.c_int32 * max(len(counts), 1))(*[int(n) for n in counts])
+
+
+def _pointer_table(pointers, count):
+    """A host table of `count` addresses (float_ptr, int or None = NULL), or NULL when `pointers` is None."""
+    if pointers is None:
+        return None
+    pointers = list(pointers)
+    if len(pointers) != count:
+        raise RuntimeError('redner: a table of %d pointers for %d vertex sets' % (len(pointers), count))
+    return (C.c_void_p * max(count, 1))(*[_addr(p) or None for p in pointers])
+
+
+def pose_scratch(counts):
+    """Not in the reference's module: (forward_floats, backward_floats), the scratch pose_vertices (without a given centre) and
+    pose_vertices_backward need for vertex sets of these sizes (rdr_pose_scratch, include/redner_amd_pose.h)."""
+    fwd, bwd = C.c_int64(0), C.c_int64(0)
+    _call(_capi.lib(), 'pose_scratch', 'rdr_pose_scratch', len(counts), _count_table(counts), C.byref(fwd), C.byref(bwd))
+    return int(fwd.value), int(bwd.value)
+
+
+def pose_plan(counts):
+    """Not in the reference's module: (chunk_vertices, max_workgroups, workgroups) of rdr_pose_plan: the vertices of a chunk, the
+    most workgroups a launch has, and how many it has for sets of these sizes (csrc/pose.h)."""
+    chunk, most, groups = C.c_int(0), C.c_int(0), C.c_int(0)
+    _call(_capi.lib(), 'pose_plan', 'rdr_pose_plan', len(counts), _count_table(counts), C.byref(chunk), C.byref(most), C.byref(groups))
+    return int(chunk.value), int(most.value), int(groups.value)
+
+
+def rotate_matrix(angles, matrix, use_gpu, gpu_index):
+    """Not in the reference's module (its gen_rotate_matrix is torch code, pyredner/transform.py): rdr_rotate_matrix.  float_ptr
+    arguments; writes matrix [3, 3].  Ordered on the current torch stream, not synchronised."""
+    _call(_capi.lib(), 'rotate_matrix', 'rdr_rotate_matrix', _addr(angles) or None, _addr(matrix) or None, _place(use_gpu, gpu_index),
+          on=(use_gpu, gpu_index))
+
+
+def rotate_matrix_backward(angles, d_matrix, d_angles, use_gpu, gpu_index):
+    """Not in the reference's module: rdr_rotate_matrix_backward.  Writes d_angles [3]."""
+    _call(_capi.lib(), 'rotate_matrix_backward', 'rdr_rotate_matrix_backward', _addr(angles) or None, _addr(d_matrix) or None,
+          _addr(d_angles) or None, _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+
+
+def pose_vertices(vertices, counts, angles, translation, center, out, saved, scratch, scratch_floats, use_gpu, gpu_index):
+    """Not in the reference's module (its scripts write the pose in torch): rdr_pose_vertices.  vertices, out: one float_ptr per
+    set; counts: the sets' sizes; center: float_ptr or None = the sets' own mean; writes every out and saved [12].  Ordered on
+    the current torch stream, not synchronised."""
+    k = len(counts)
+    _call(_capi.lib(), 'pose_vertices', 'rdr_pose_vertices', k, _pointer_table(vertices, k), _count_table(counts), _addr(angles) or None,
+          _addr(translation) or None, _addr(center) or None, _pointer_table(out, k), _addr(saved) or None, _addr(scratch) or None,
+          int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+
+
+def pose_vertices_backward(vertices, counts, angles, saved, own_center, d_out, d_vertices, d_angles, d_translation, d_center, scratch,
+                           scratch_floats, use_gpu, gpu_index):
+    """Not in the reference's module: rdr_pose_vertices_backward.  d_out: per set a float_ptr or None = zeros; d_vertices: None, or
+    per set a float_ptr or None = not wanted; writes d_angles, d_translation, d_center (a given centre) and the d_vertices."""
+    k = len(counts)
+    _call(_capi.lib(), 'pose_vertices_backward', 'rdr_pose_vertices_backward', k, _pointer_table(vertices, k), _count_table(counts),
+          _addr(angles) or None, _addr(saved) or None, int(bool(own_center)), _pointer_table(d_out, k), _pointer_table(d_vertices, k),
+          _addr(d_angles) or None, _addr(d_translation) or None, _addr(d_center) or None, _addr(scratch) or None, int(scratch_floats),
+          _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+
+
 def envmap_tables(texels, y_weight, sample_cdf_ys, sample_cdf_xs, height, width, use_gpu, gpu_index):
     """Not in the reference's module (its tables are torch code, pyredner/envmap.py): rdr_envmap_tables.  float_ptr arguments;
     writes both tables and returns the last unnormalised entry of the column table (one synchronisation)."""
