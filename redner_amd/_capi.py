@@ -145,86 +145,80 @@ class DeferredDesc(C.Structure):
 DL_AMBIENT, DL_POINT, DL_DIRECTIONAL, DL_SPOT = range(4)
 
 _p, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
-# Every symbol of include/redner_amd.h: name -> (restype, argtypes).  load() sets both on each function; a handle or pointer
-# without argtypes would go through ctypes' default int conversion (tests/test_capi.py compares this table with the header).
-SIGNATURES = {
-    'rdr_last_error': (C.c_char_p, []),
-    'rdr_scene_create': (_p, [C.POINTER(CameraDesc), C.POINTER(ShapeDesc), _i, C.POINTER(MaterialDesc), _i,
-                              C.POINTER(AreaLightDesc), _i, C.POINTER(EnvmapDesc), _i, _i, _i, _i]),
-    'rdr_scene_destroy': (None, [_p]),
-    'rdr_scene_max_generic_texture_dimension': (_i, [_p]),
-    'rdr_render': (_i, [_p, C.POINTER(RenderOptionsDesc), _p, _p, C.POINTER(DSceneDesc), _p, _p]),
-    'rdr_compute_num_channels': (_i, [C.POINTER(C.c_int), _i, _i]),
-    'rdr_trace_stats_enable': (None, [_i, _i]),
-    'rdr_trace_stats_reset': (None, []),
-    'rdr_trace_stats_get': (None, [C.POINTER(TraceStats)]),
-    'rdr_scene_trace': (_i, [_p, _p, _p, _i, _i]),
-    'rdr_trim_cache': (C.c_uint64, []),
-    'rdr_set_stream': (None, [_p]),
-    'rdr_set_pool_cap_mb': (None, [_i64]),
-    'rdr_get_pool_cap_mb': (_i64, []),
-    'rdr_set_build_flags': (None, [C.c_uint]),
-    'rdr_libm_exact': (_i, []),
-    'rdr_deferred_shade': (_i, [C.POINTER(DeferredDesc), _p, _p, _p]),
-    'rdr_deferred_shade_backward': (_i, [C.POINTER(DeferredDesc), _p, _p, _p, _p, _p]),
-    'rdr_mip_num_levels': (_i, [_i, _i]),
-    'rdr_mip_backward_scratch': (_i64, [_i, _i, _i]),
-    'rdr_mip_tiled_stages': (_i, [_i, _i, _i]),
-    'rdr_mip_pyramid': (_i, [_i, _i, _i, _i, C.POINTER(_p), _i]),
-    'rdr_mip_pyramid_backward': (_i, [_i, _i, _i, _i, C.POINTER(_p), _p, _p, _i64, _i]),
-    'rdr_sh_backward_scratch': (_i64, [_i] * 4),
-    'rdr_sh_reconstruct': (_i, [_p] + [_i] * 4 + [_p, _p, _i]),
-    'rdr_sh_reconstruct_backward': (_i, [_p, _p] + [_i] * 4 + [_p, _p, _i64, _i]),
-    'rdr_envmap_tables': (_i, [_p, _p, _i, _i, _p, _p, C.POINTER(C.c_float), _i]),
-    'rdr_mesh_topology_create': (_p, [_p, _i, _i, _i, _i]),
-    'rdr_mesh_topology_destroy': (None, [_p]),
-    'rdr_mesh_topology_read': (_i, [_p, _p, _p]),
-    'rdr_vertex_normal_scratch': (_i, [_p, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
-    'rdr_vertex_normal': (_i, [_p, _i, _p, _p, _p, _p, _i64]),
-    'rdr_vertex_normal_backward': (_i, [_p, _i, _p, _p, _p, _p, _p, _i64]),
-    'rdr_debug_counters_get': (None, [C.POINTER(DebugCounters)]),
-    'rdr_debug_dump_edges': (_i, [_p, C.c_char_p]),
-    'rdr_debug_bvh_check': (_i, [_p]),
-    'rdr_debug_libm': (_i, [_i, _p, _p, _p, _i]),
-    'rdr_debug_trace_plan': (_i, [_i] * 8 + [C.POINTER(Tuning), _p]),
-    'rdr_debug_scene_trace_plan': (_i, [_p] + [_i] * 4 + [C.POINTER(Tuning), _p]),
-    'rdr_debug_grad_scatter': (_i, [_p, C.POINTER(DSceneDesc), C.c_uint64, _i, _i, _i, _p, _p, _p, _p]),
-    'rdr_debug_compact': (_i, [_i, _i, _p, _p] + [_i] * 6 + [_p] * 3),
-    'rdr_debug_walk': (_i, [_i, _i, _i, _p] + [_i] * 5 + [_p] * 4),
-    'rdr_debug_sort_pairs': (_i, [_p, _p, _i, _p, _p]),
-}
-EXPORTS = tuple(SIGNATURES)
-# Every symbol of include/redner_amd_mesh.h, the companion header (Laplacian smoothing, csrc/mesh_smooth.h): the same form, the same
-# library; load() requires and binds them like the ones above (tests/test_mesh_smooth.py compares this table with that header).
-MESH_SIGNATURES = {
-    'rdr_mesh_boundary': (_i, [_p, _p]),
-    'rdr_mesh_smooth_scratch': (_i, [_p, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
-    'rdr_mesh_laplacian': (_i, [_p, _i, _p, _p, _p, _p, _p, _i64]),
-    'rdr_mesh_laplacian_backward': (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64]),
-    'rdr_mesh_smooth': (_i, [_p, _i, _p, _p, C.c_float, _i, _p, _p, _i64]),
-}
-# Every symbol of include/redner_amd_image.h, the second companion header (the Gaussian pyramid loss, csrc/pyramid_loss.h): the same
-# form again (tests/test_pyramid_loss.py compares this table with that header).
-IMAGE_SIGNATURES = {
-    'rdr_pyramid_loss_scratch': (_i, [_i] * 5 + [C.POINTER(_i64), C.POINTER(_i64)]),
-    'rdr_pyramid_loss_plan': (_i, [_i] * 5 + [C.POINTER(_i), C.POINTER(_i)]),
-    'rdr_pyramid_loss': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _p, _p, _i64, _i]),
-    'rdr_pyramid_loss_backward': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _i64, _p, _p, _p, _p, _i64, _i]),
-}
-# Every symbol of include/redner_amd_pose.h, the third companion header (the rigid pose, csrc/pose.h): the same form again
-# (tests/test_pose.py compares this table with that header).
-POSE_SIGNATURES = {
-    'rdr_pose_scratch': (_i, [_i, c_int_p, C.POINTER(_i64), C.POINTER(_i64)]),
-    'rdr_pose_plan': (_i, [_i, c_int_p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
-    'rdr_rotate_matrix': (_i, [_p, _p, _i]),
-    'rdr_rotate_matrix_backward': (_i, [_p, _p, _p, _i]),
-    'rdr_pose_vertices': (_i, [_i, C.POINTER(_p), c_int_p, _p, _p, _p, C.POINTER(_p), _p, _p, _i64, _i]),
-    'rdr_pose_vertices_backward': (_i, [_i, C.POINTER(_p), c_int_p, _p, _p, _i, C.POINTER(_p), C.POINTER(_p), _p, _p, _p, _p, _i64, _i]),
-}
-# Every symbol of include/redner_amd_debug.h, the companion header of the test hooks that came after redner_amd.h was fixed: the same
-# form again (tests/test_lane_park.py compares this table with that header).
-DEBUG_SIGNATURES = {
-    'rdr_debug_lane_park': (_i, [_i, _p, _p, _p, _p]),
+# Every function of the C ABI, under the header of include/ that declares it: header -> {name: (restype, argtypes)}.  load()
+# requires every name of the loaded library and sets both on each function; a handle or pointer without argtypes would go through
+# ctypes' default int conversion (tests/test_capi.py compares this table with the headers and the libraries' exports).
+HEADERS = {
+    'redner_amd.h': {
+        'rdr_last_error': (C.c_char_p, []),
+        'rdr_scene_create': (_p, [C.POINTER(CameraDesc), C.POINTER(ShapeDesc), _i, C.POINTER(MaterialDesc), _i,
+                                  C.POINTER(AreaLightDesc), _i, C.POINTER(EnvmapDesc), _i, _i, _i, _i]),
+        'rdr_scene_destroy': (None, [_p]),
+        'rdr_scene_max_generic_texture_dimension': (_i, [_p]),
+        'rdr_render': (_i, [_p, C.POINTER(RenderOptionsDesc), _p, _p, C.POINTER(DSceneDesc), _p, _p]),
+        'rdr_compute_num_channels': (_i, [C.POINTER(C.c_int), _i, _i]),
+        'rdr_trace_stats_enable': (None, [_i, _i]),
+        'rdr_trace_stats_reset': (None, []),
+        'rdr_trace_stats_get': (None, [C.POINTER(TraceStats)]),
+        'rdr_scene_trace': (_i, [_p, _p, _p, _i, _i]),
+        'rdr_trim_cache': (C.c_uint64, []),
+        'rdr_set_stream': (None, [_p]),
+        'rdr_set_pool_cap_mb': (None, [_i64]),
+        'rdr_get_pool_cap_mb': (_i64, []),
+        'rdr_set_build_flags': (None, [C.c_uint]),
+        'rdr_libm_exact': (_i, []),
+        'rdr_deferred_shade': (_i, [C.POINTER(DeferredDesc), _p, _p, _p]),
+        'rdr_deferred_shade_backward': (_i, [C.POINTER(DeferredDesc), _p, _p, _p, _p, _p]),
+        'rdr_mip_num_levels': (_i, [_i, _i]),
+        'rdr_mip_backward_scratch': (_i64, [_i, _i, _i]),
+        'rdr_mip_tiled_stages': (_i, [_i, _i, _i]),
+        'rdr_mip_pyramid': (_i, [_i, _i, _i, _i, C.POINTER(_p), _i]),
+        'rdr_mip_pyramid_backward': (_i, [_i, _i, _i, _i, C.POINTER(_p), _p, _p, _i64, _i]),
+        'rdr_sh_backward_scratch': (_i64, [_i] * 4),
+        'rdr_sh_reconstruct': (_i, [_p] + [_i] * 4 + [_p, _p, _i]),
+        'rdr_sh_reconstruct_backward': (_i, [_p, _p] + [_i] * 4 + [_p, _p, _i64, _i]),
+        'rdr_envmap_tables': (_i, [_p, _p, _i, _i, _p, _p, C.POINTER(C.c_float), _i]),
+        'rdr_mesh_topology_create': (_p, [_p, _i, _i, _i, _i]),
+        'rdr_mesh_topology_destroy': (None, [_p]),
+        'rdr_mesh_topology_read': (_i, [_p, _p, _p]),
+        'rdr_vertex_normal_scratch': (_i, [_p, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+        'rdr_vertex_normal': (_i, [_p, _i, _p, _p, _p, _p, _i64]),
+        'rdr_vertex_normal_backward': (_i, [_p, _i, _p, _p, _p, _p, _p, _i64]),
+        'rdr_debug_counters_get': (None, [C.POINTER(DebugCounters)]),
+        'rdr_debug_dump_edges': (_i, [_p, C.c_char_p]),
+        'rdr_debug_bvh_check': (_i, [_p]),
+        'rdr_debug_libm': (_i, [_i, _p, _p, _p, _i]),
+        'rdr_debug_trace_plan': (_i, [_i] * 8 + [C.POINTER(Tuning), _p]),
+        'rdr_debug_scene_trace_plan': (_i, [_p] + [_i] * 4 + [C.POINTER(Tuning), _p]),
+        'rdr_debug_grad_scatter': (_i, [_p, C.POINTER(DSceneDesc), C.c_uint64, _i, _i, _i, _p, _p, _p, _p]),
+        'rdr_debug_compact': (_i, [_i, _i, _p, _p] + [_i] * 6 + [_p] * 3),
+        'rdr_debug_walk': (_i, [_i, _i, _i, _p] + [_i] * 5 + [_p] * 4),
+        'rdr_debug_sort_pairs': (_i, [_p, _p, _i, _p, _p]),
+    },
+    'redner_amd_mesh.h': {                   # Laplacian smoothing (csrc/mesh_smooth.h)
+        'rdr_mesh_boundary': (_i, [_p, _p]),
+        'rdr_mesh_smooth_scratch': (_i, [_p, _i, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+        'rdr_mesh_laplacian': (_i, [_p, _i, _p, _p, _p, _p, _p, _i64]),
+        'rdr_mesh_laplacian_backward': (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i64]),
+        'rdr_mesh_smooth': (_i, [_p, _i, _p, _p, C.c_float, _i, _p, _p, _i64]),
+    },
+    'redner_amd_image.h': {                  # the Gaussian pyramid loss (csrc/pyramid_loss.h)
+        'rdr_pyramid_loss_scratch': (_i, [_i] * 5 + [C.POINTER(_i64), C.POINTER(_i64)]),
+        'rdr_pyramid_loss_plan': (_i, [_i] * 5 + [C.POINTER(_i), C.POINTER(_i)]),
+        'rdr_pyramid_loss': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _p, _p, _i64, _i]),
+        'rdr_pyramid_loss_backward': (_i, [_p, _p] + [_i] * 5 + [c_float_p, C.c_float, _p, _i64, _p, _p, _p, _p, _i64, _i]),
+    },
+    'redner_amd_pose.h': {                   # the rigid pose (csrc/pose.h)
+        'rdr_pose_scratch': (_i, [_i, c_int_p, C.POINTER(_i64), C.POINTER(_i64)]),
+        'rdr_pose_plan': (_i, [_i, c_int_p, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+        'rdr_rotate_matrix': (_i, [_p, _p, _i]),
+        'rdr_rotate_matrix_backward': (_i, [_p, _p, _p, _i]),
+        'rdr_pose_vertices': (_i, [_i, C.POINTER(_p), c_int_p, _p, _p, _p, C.POINTER(_p), _p, _p, _i64, _i]),
+        'rdr_pose_vertices_backward': (_i, [_i, C.POINTER(_p), c_int_p, _p, _p, _i, C.POINTER(_p), C.POINTER(_p), _p, _p, _p, _p, _i64, _i]),
+    },
+    'redner_amd_debug.h': {                  # test hooks that came after redner_amd.h was fixed
+        'rdr_debug_lane_park': (_i, [_i, _p, _p, _p, _p]),
+    },
 }
 
 # rdr_scatter_op / rdr_scatter_target (rdr_debug_grad_scatter)
@@ -248,11 +242,11 @@ def load(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % path)
     lib = C.CDLL(path)
-    for name in EXPORTS + tuple(MESH_SIGNATURES) + tuple(IMAGE_SIGNATURES) + tuple(POSE_SIGNATURES) + tuple(DEBUG_SIGNATURES):
+    signatures = [item for table in HEADERS.values() for item in table.items()]
+    for name, _ in signatures:
         if not hasattr(lib, name):
             raise RuntimeError("redner_amd: %s does not export %s" % (path, name))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(IMAGE_SIGNATURES.items()) + \
-            list(POSE_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+    for name, (restype, argtypes) in signatures:
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib, _lib_path = lib, path

@@ -20,12 +20,7 @@ library raises for them.
 import torch
 
 from . import redner as _default_backend
-
-
-def _place(t):
-    use_gpu = t.device.type == 'cuda'
-    index = t.device.index if t.device.index is not None else (torch.cuda.current_device() if use_gpu else 0)
-    return use_gpu, index
+from ._op import named, place, ptr, scratch, upstream
 
 
 def _geometry(image):
@@ -34,17 +29,16 @@ def _geometry(image):
 
 
 def _forward(rd, image, target, num_levels, clamp, weights):
-    """image, target: detached contiguous fp32.  -> loss (0-dim fp32), terms (fp64 [L]), scratch (fp64; the levels at its start)"""
+    """image, target: detached contiguous fp32.  -> loss (0-dim fp32), terms (fp64 [L]), saved (fp64; the levels at its start)"""
     batch, height, width, channels = _geometry(image)
-    use_gpu, index = _place(image)
+    use_gpu, index = place(image)
     fwd, _ = rd.pyramid_loss_scratch(batch, height, width, channels, num_levels)
-    scratch = torch.empty((fwd + 1) // 2, dtype=torch.float64, device=image.device)
+    saved = scratch(fwd, image.device)
     loss = torch.empty((), dtype=torch.float32, device=image.device)
     terms = torch.empty(num_levels, dtype=torch.float64, device=image.device)
-    rd.pyramid_loss(rd.float_ptr(image.data_ptr()), rd.float_ptr(target.data_ptr()), rd.float_ptr(loss.data_ptr()), terms.data_ptr(),
-                    rd.float_ptr(scratch.data_ptr()), fwd, batch, height, width, channels, num_levels, weights, clamp or 0.0,
-                    use_gpu, index)
-    return loss, terms, scratch
+    rd.pyramid_loss(ptr(rd, image), ptr(rd, target), ptr(rd, loss), terms.data_ptr(), ptr(rd, saved), fwd, batch, height, width,
+                    channels, num_levels, weights, clamp or 0.0, use_gpu, index)
+    return loss, terms, saved
 
 
 class GaussianPyramidLoss(torch.autograd.Function):
@@ -55,9 +49,9 @@ class GaussianPyramidLoss(torch.autograd.Function):
     def forward(ctx, image, target, num_levels, clamp, weights, backend=None):
         rd = backend or _default_backend
         a, b = image.detach().contiguous(), target.detach().contiguous()
-        loss, terms, scratch = _forward(rd, a, b, num_levels, clamp, weights)
+        loss, terms, saved = _forward(rd, a, b, num_levels, clamp, weights)
         ctx.rd, ctx.options = rd, (num_levels, clamp, weights)
-        ctx.image, ctx.target, ctx.scratch = a, b, scratch
+        ctx.image, ctx.target, ctx.scratch = a, b, saved
         ctx.mark_non_differentiable(terms)
         return loss, terms
 
@@ -66,16 +60,15 @@ class GaussianPyramidLoss(torch.autograd.Function):
         rd, a, b = ctx.rd, ctx.image, ctx.target
         num_levels, clamp, weights = ctx.options
         batch, height, width, channels = _geometry(a)
-        use_gpu, index = _place(a)
-        upstream = d_loss.to(device=a.device, dtype=torch.float32).contiguous()
+        use_gpu, index = place(a)
+        g = upstream(d_loss, a.device)
         d_image = torch.empty_like(a)
         d_target = torch.empty_like(b) if ctx.needs_input_grad[1] else None
         _, bwd = rd.pyramid_loss_scratch(batch, height, width, channels, num_levels)
-        scratch = torch.empty(max(bwd, 1), dtype=torch.float32, device=a.device)
-        rd.pyramid_loss_backward(rd.float_ptr(a.data_ptr()), rd.float_ptr(b.data_ptr()), rd.float_ptr(ctx.scratch.data_ptr()),
-                                 2 * ctx.scratch.numel(), rd.float_ptr(upstream.data_ptr()), rd.float_ptr(d_image.data_ptr()),
-                                 None if d_target is None else rd.float_ptr(d_target.data_ptr()), rd.float_ptr(scratch.data_ptr()),
-                                 bwd, batch, height, width, channels, num_levels, weights, clamp or 0.0, use_gpu, index)
+        work = scratch(bwd, a.device)
+        rd.pyramid_loss_backward(ptr(rd, a), ptr(rd, b), ptr(rd, ctx.scratch), 2 * ctx.scratch.numel(), ptr(rd, g), ptr(rd, d_image),
+                                 ptr(rd, d_target), ptr(rd, work), bwd, batch, height, width, channels, num_levels, weights,
+                                 clamp or 0.0, use_gpu, index)
         return (d_image if ctx.needs_input_grad[0] else None), d_target, None, None, None, None
 
 
@@ -113,10 +106,8 @@ def gaussian_pyramid_loss(image, target, num_levels=5, clamp=None, weights=None,
     level (a coarse-to-fine schedule).  With return_terms=True also the detached fp64 [num_levels] per-level terms, summed over
     the batch."""
     num_levels, clamp, weights = _checked(image, target, num_levels, clamp, weights)
-    try:
+    with named('gaussian_pyramid_loss'):
         loss, terms = GaussianPyramidLoss.apply(image, target, num_levels, clamp, weights, backend)
-    except RuntimeError as e:
-        raise RuntimeError('gaussian_pyramid_loss: %s' % e) from e
     return (loss, terms) if return_terms else loss
 
 
@@ -125,8 +116,8 @@ def pyramid_levels(image, target, num_levels=5, clamp=None, backend=None):
     num_levels, clamp, _ = _checked(image, target, num_levels, clamp, None)
     rd = backend or _default_backend
     a, b = image.detach().contiguous(), target.detach().contiguous()
-    _, _, scratch = _forward(rd, a, b, num_levels, clamp, None)
-    flat = scratch.view(torch.float32)
+    _, _, saved = _forward(rd, a, b, num_levels, clamp, None)
+    flat = saved.view(torch.float32)
     batch, height, width, channels = _geometry(a)
     levels, at = [], 0
     for _ in range(1, num_levels):

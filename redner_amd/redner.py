@@ -30,6 +30,13 @@ def _addr(p):
     return int(p)
 
 
+def _ptr(p):
+    """The address as a c_void_p argument of the C ABI takes it: None for NULL (a null float_ptr included)"""
+    if p is None:
+        return None
+    return (p.addr if isinstance(p, (float_ptr, int_ptr)) else int(p)) or None
+
+
 class float_ptr:                       # src/redner.cpp:23-24, src/ptr.h:10-24
     def __init__(self, addr):
         self.addr = int(addr)
@@ -421,7 +428,7 @@ def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, im
         raise RuntimeError('redner.deferred_shade: %d light ranges for %d images' % (len(image_light_ranges), d.num_images))
     ranges = (C.c_int32 * max(len(flat), 1))(*flat)
     d.light_type, d.image_light_range = types, ranges
-    d.gpu_index = _place(use_gpu, gpu_index)
+    d.gpu_index = _gpu_index(use_gpu, gpu_index)
     return d, (types, ranges)
 
 
@@ -431,7 +438,7 @@ def deferred_shade(g_buffer, light_params, image, num_images, height, width, aa_
     light_params [L, 10], image [N, H, W, 3 + alpha]: float_ptr; light_types: L DeferredLightType; image_light_ranges: N
     (begin, end) pairs into the table."""
     d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index)
-    _call(_capi.lib(), 'deferred_shade', 'rdr_deferred_shade', C.byref(d), _addr(g_buffer), _addr(light_params), _addr(image),
+    _call(_capi.lib(), 'deferred_shade', 'rdr_deferred_shade', C.byref(d), _ptr(g_buffer), _ptr(light_params), _ptr(image),
           on=(use_gpu, gpu_index))
 
 
@@ -439,8 +446,8 @@ def deferred_shade_backward(g_buffer, light_params, d_image, d_g_buffer, d_light
                             aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index):
     """Not in the reference: rdr_deferred_shade_backward; writes every element of d_g_buffer and d_light_params."""
     d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index)
-    _call(_capi.lib(), 'deferred_shade_backward', 'rdr_deferred_shade_backward', C.byref(d), _addr(g_buffer), _addr(light_params),
-          _addr(d_image), _addr(d_g_buffer), _addr(d_light_params), on=(use_gpu, gpu_index))
+    _call(_capi.lib(), 'deferred_shade_backward', 'rdr_deferred_shade_backward', C.byref(d), _ptr(g_buffer), _ptr(light_params),
+          _ptr(d_image), _ptr(d_g_buffer), _ptr(d_light_params), on=(use_gpu, gpu_index))
 
 
 def mip_num_levels(height, width):
@@ -462,7 +469,7 @@ def mip_tiled_stages(height, width, channels):
 
 
 def _level_table(levels):
-    return (C.c_void_p * max(len(levels), 1))(*[_addr(l) or None for l in levels])
+    return (C.c_void_p * max(len(levels), 1))(*[_ptr(l) for l in levels])
 
 
 def mip_pyramid(levels, height, width, channels, use_gpu, gpu_index):
@@ -470,14 +477,14 @@ def mip_pyramid(levels, height, width, channels, use_gpu, gpu_index):
     levels: float_ptr of every level, [0] the image [height, width, channels]; levels 1.. are written.  Ordered on the
     current torch stream, not synchronised."""
     _call(_capi.lib(), 'mip_pyramid', 'rdr_mip_pyramid', int(height), int(width), int(channels), len(levels), _level_table(levels),
-          _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+          _gpu_index(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def mip_pyramid_backward(d_levels, d_texels, scratch, scratch_floats, height, width, channels, use_gpu, gpu_index):
     """Not in the reference's module: rdr_mip_pyramid_backward.  d_levels: float_ptr per level, float_ptr(0) = zeros; writes every
     element of d_texels."""
     _call(_capi.lib(), 'mip_pyramid_backward', 'rdr_mip_pyramid_backward', int(height), int(width), int(channels), len(d_levels),
-          _level_table(d_levels), _addr(d_texels), _addr(scratch), int(scratch_floats), _place(use_gpu, gpu_index),
+          _level_table(d_levels), _ptr(d_texels), _ptr(scratch), int(scratch_floats), _gpu_index(use_gpu, gpu_index),
           on=(use_gpu, gpu_index))
 
 
@@ -491,34 +498,30 @@ def sh_reconstruct(coeffs, image, clamp, channels, num_coeffs, height, width, us
     """Not in the reference's module (its SH_reconstruct is torch code, pyredner/utils.py): rdr_sh_reconstruct
     (include/redner_amd.h).  coeffs: float_ptr of [channels, num_coeffs]; writes image [height, width, channels] and, unless it
     is None, the clamp bytes.  Ordered on the current torch stream, not synchronised."""
-    _call(_capi.lib(), 'sh_reconstruct', 'rdr_sh_reconstruct', _addr(coeffs) or None, int(channels), int(num_coeffs), int(height),
-          int(width), _addr(image) or None, _addr(clamp) or None, _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+    _call(_capi.lib(), 'sh_reconstruct', 'rdr_sh_reconstruct', _ptr(coeffs), int(channels), int(num_coeffs), int(height),
+          int(width), _ptr(image), _ptr(clamp), _gpu_index(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def sh_reconstruct_backward(clamp, d_image, d_coeffs, scratch, scratch_floats, channels, num_coeffs, height, width, use_gpu,
                             gpu_index):
     """Not in the reference's module: rdr_sh_reconstruct_backward.  Writes every element of d_coeffs [channels, num_coeffs]."""
-    _call(_capi.lib(), 'sh_reconstruct_backward', 'rdr_sh_reconstruct_backward', _addr(clamp) or None, _addr(d_image) or None,
-          int(channels), int(num_coeffs), int(height), int(width), _addr(d_coeffs) or None, _addr(scratch) or None,
-          int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+    _call(_capi.lib(), 'sh_reconstruct_backward', 'rdr_sh_reconstruct_backward', _ptr(clamp), _ptr(d_image),
+          int(channels), int(num_coeffs), int(height), int(width), _ptr(d_coeffs), _ptr(scratch),
+          int(scratch_floats), _gpu_index(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def pyramid_loss_scratch(batch, height, width, channels, num_levels):
     """Not in the reference's module: (forward_floats, backward_floats), the scratch pyramid_loss and pyramid_loss_backward need
     (rdr_pyramid_loss_scratch, include/redner_amd_image.h)."""
-    fwd, bwd = C.c_int64(0), C.c_int64(0)
-    _call(_capi.lib(), 'pyramid_loss_scratch', 'rdr_pyramid_loss_scratch', int(batch), int(height), int(width), int(channels),
-          int(num_levels), C.byref(fwd), C.byref(bwd))
-    return int(fwd.value), int(bwd.value)
+    return _outputs(C.c_int64, 2, _capi.lib(), 'pyramid_loss_scratch', 'rdr_pyramid_loss_scratch', int(batch), int(height), int(width),
+                    int(channels), int(num_levels))
 
 
 def pyramid_loss_plan(batch, height, width, channels, num_levels):
     """Not in the reference's module: (tiled_levels, small_floats) of rdr_pyramid_loss_plan: how many leading levels the tiled
     kernels do, and the floats per image at or below which a level is left to the one workgroup per image (csrc/pyramid_loss.h)."""
-    tiled, small = C.c_int(0), C.c_int(0)
-    _call(_capi.lib(), 'pyramid_loss_plan', 'rdr_pyramid_loss_plan', int(batch), int(height), int(width), int(channels),
-          int(num_levels), C.byref(tiled), C.byref(small))
-    return int(tiled.value), int(small.value)
+    return _outputs(C.c_int, 2, _capi.lib(), 'pyramid_loss_plan', 'rdr_pyramid_loss_plan', int(batch), int(height), int(width),
+                    int(channels), int(num_levels))
 
 
 def _weight_table(weights, num_levels):
@@ -530,18 +533,18 @@ def pyramid_loss(image, target, loss, terms, scratch, scratch_floats, batch, hei
     """Not in the reference's module (its scripts write the loss in torch): rdr_pyramid_loss.  image, target, loss, scratch:
     float_ptr; terms: the address of num_levels doubles or None; weights: num_levels numbers or None; clamp: 0 = none.  Ordered
     on the current torch stream, not synchronised."""
-    _call(_capi.lib(), 'pyramid_loss', 'rdr_pyramid_loss', _addr(image) or None, _addr(target) or None, int(batch), int(height),
-          int(width), int(channels), int(num_levels), _weight_table(weights, num_levels), float(clamp), _addr(loss) or None,
-          _addr(terms) or None, _addr(scratch) or None, int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+    _call(_capi.lib(), 'pyramid_loss', 'rdr_pyramid_loss', _ptr(image), _ptr(target), int(batch), int(height),
+          int(width), int(channels), int(num_levels), _weight_table(weights, num_levels), float(clamp), _ptr(loss),
+          _ptr(terms), _ptr(scratch), int(scratch_floats), _gpu_index(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def pyramid_loss_backward(image, target, saved, saved_floats, upstream, d_image, d_target, scratch, scratch_floats, batch, height,
                           width, channels, num_levels, weights, clamp, use_gpu, gpu_index):
     """Not in the reference's module: rdr_pyramid_loss_backward.  Writes every element of d_image and, unless None, d_target."""
-    _call(_capi.lib(), 'pyramid_loss_backward', 'rdr_pyramid_loss_backward', _addr(image) or None, _addr(target) or None, int(batch),
+    _call(_capi.lib(), 'pyramid_loss_backward', 'rdr_pyramid_loss_backward', _ptr(image), _ptr(target), int(batch),
           int(height), int(width), int(channels), int(num_levels), _weight_table(weights, num_levels), float(clamp),
-          _addr(saved) or None, int(saved_floats), _addr(upstream) or None, _addr(d_image) or None, _addr(d_target) or None,
-          _addr(scratch) or None, int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+          _ptr(saved), int(saved_floats), _ptr(upstream), _ptr(d_image), _ptr(d_target),
+          _ptr(scratch), int(scratch_floats), _gpu_index(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def _count_table(counts):
@@ -555,36 +558,32 @@ def _pointer_table(pointers, count):
     pointers = list(pointers)
     if len(pointers) != count:
         raise RuntimeError('redner: a table of %d pointers for %d vertex sets' % (len(pointers), count))
-    return (C.c_void_p * max(count, 1))(*[_addr(p) or None for p in pointers])
+    return (C.c_void_p * max(count, 1))(*[_ptr(p) for p in pointers])
 
 
 def pose_scratch(counts):
     """Not in the reference's module: (forward_floats, backward_floats), the scratch pose_vertices (without a given centre) and
     pose_vertices_backward need for vertex sets of these sizes (rdr_pose_scratch, include/redner_amd_pose.h)."""
-    fwd, bwd = C.c_int64(0), C.c_int64(0)
-    _call(_capi.lib(), 'pose_scratch', 'rdr_pose_scratch', len(counts), _count_table(counts), C.byref(fwd), C.byref(bwd))
-    return int(fwd.value), int(bwd.value)
+    return _outputs(C.c_int64, 2, _capi.lib(), 'pose_scratch', 'rdr_pose_scratch', len(counts), _count_table(counts))
 
 
 def pose_plan(counts):
     """Not in the reference's module: (chunk_vertices, max_workgroups, workgroups) of rdr_pose_plan: the vertices of a chunk, the
     most workgroups a launch has, and how many it has for sets of these sizes (csrc/pose.h)."""
-    chunk, most, groups = C.c_int(0), C.c_int(0), C.c_int(0)
-    _call(_capi.lib(), 'pose_plan', 'rdr_pose_plan', len(counts), _count_table(counts), C.byref(chunk), C.byref(most), C.byref(groups))
-    return int(chunk.value), int(most.value), int(groups.value)
+    return _outputs(C.c_int, 3, _capi.lib(), 'pose_plan', 'rdr_pose_plan', len(counts), _count_table(counts))
 
 
 def rotate_matrix(angles, matrix, use_gpu, gpu_index):
     """Not in the reference's module (its gen_rotate_matrix is torch code, pyredner/transform.py): rdr_rotate_matrix.  float_ptr
     arguments; writes matrix [3, 3].  Ordered on the current torch stream, not synchronised."""
-    _call(_capi.lib(), 'rotate_matrix', 'rdr_rotate_matrix', _addr(angles) or None, _addr(matrix) or None, _place(use_gpu, gpu_index),
+    _call(_capi.lib(), 'rotate_matrix', 'rdr_rotate_matrix', _ptr(angles), _ptr(matrix), _gpu_index(use_gpu, gpu_index),
           on=(use_gpu, gpu_index))
 
 
 def rotate_matrix_backward(angles, d_matrix, d_angles, use_gpu, gpu_index):
     """Not in the reference's module: rdr_rotate_matrix_backward.  Writes d_angles [3]."""
-    _call(_capi.lib(), 'rotate_matrix_backward', 'rdr_rotate_matrix_backward', _addr(angles) or None, _addr(d_matrix) or None,
-          _addr(d_angles) or None, _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+    _call(_capi.lib(), 'rotate_matrix_backward', 'rdr_rotate_matrix_backward', _ptr(angles), _ptr(d_matrix),
+          _ptr(d_angles), _gpu_index(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def pose_vertices(vertices, counts, angles, translation, center, out, saved, scratch, scratch_floats, use_gpu, gpu_index):
@@ -592,9 +591,9 @@ def pose_vertices(vertices, counts, angles, translation, center, out, saved, scr
     set; counts: the sets' sizes; center: float_ptr or None = the sets' own mean; writes every out and saved [12].  Ordered on
     the current torch stream, not synchronised."""
     k = len(counts)
-    _call(_capi.lib(), 'pose_vertices', 'rdr_pose_vertices', k, _pointer_table(vertices, k), _count_table(counts), _addr(angles) or None,
-          _addr(translation) or None, _addr(center) or None, _pointer_table(out, k), _addr(saved) or None, _addr(scratch) or None,
-          int(scratch_floats), _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+    _call(_capi.lib(), 'pose_vertices', 'rdr_pose_vertices', k, _pointer_table(vertices, k), _count_table(counts), _ptr(angles),
+          _ptr(translation), _ptr(center), _pointer_table(out, k), _ptr(saved), _ptr(scratch),
+          int(scratch_floats), _gpu_index(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def pose_vertices_backward(vertices, counts, angles, saved, own_center, d_out, d_vertices, d_angles, d_translation, d_center, scratch,
@@ -603,17 +602,17 @@ def pose_vertices_backward(vertices, counts, angles, saved, own_center, d_out, d
     per set a float_ptr or None = not wanted; writes d_angles, d_translation, d_center (a given centre) and the d_vertices."""
     k = len(counts)
     _call(_capi.lib(), 'pose_vertices_backward', 'rdr_pose_vertices_backward', k, _pointer_table(vertices, k), _count_table(counts),
-          _addr(angles) or None, _addr(saved) or None, int(bool(own_center)), _pointer_table(d_out, k), _pointer_table(d_vertices, k),
-          _addr(d_angles) or None, _addr(d_translation) or None, _addr(d_center) or None, _addr(scratch) or None, int(scratch_floats),
-          _place(use_gpu, gpu_index), on=(use_gpu, gpu_index))
+          _ptr(angles), _ptr(saved), int(bool(own_center)), _pointer_table(d_out, k), _pointer_table(d_vertices, k),
+          _ptr(d_angles), _ptr(d_translation), _ptr(d_center), _ptr(scratch), int(scratch_floats),
+          _gpu_index(use_gpu, gpu_index), on=(use_gpu, gpu_index))
 
 
 def envmap_tables(texels, y_weight, sample_cdf_ys, sample_cdf_xs, height, width, use_gpu, gpu_index):
     """Not in the reference's module (its tables are torch code, pyredner/envmap.py): rdr_envmap_tables.  float_ptr arguments;
     writes both tables and returns the last unnormalised entry of the column table (one synchronisation)."""
     total = C.c_float(0.0)
-    _call(_capi.lib(), 'envmap_tables', 'rdr_envmap_tables', _addr(texels) or None, _addr(y_weight) or None, int(height), int(width),
-          _addr(sample_cdf_ys) or None, _addr(sample_cdf_xs) or None, C.byref(total), _place(use_gpu, gpu_index),
+    _call(_capi.lib(), 'envmap_tables', 'rdr_envmap_tables', _ptr(texels), _ptr(y_weight), int(height), int(width),
+          _ptr(sample_cdf_ys), _ptr(sample_cdf_xs), C.byref(total), _gpu_index(use_gpu, gpu_index),
           on=(use_gpu, gpu_index))
     return float(total.value)
 
@@ -634,7 +633,7 @@ class mesh_topology:
         self.lib, self.handle = _capi.lib(), None
         self.num_triangles, self.num_vertices = int(num_triangles), int(num_vertices)
         self.use_gpu, self.gpu_index = bool(use_gpu), int(gpu_index)
-        self.handle = _call(self.lib, 'mesh_topology', 'rdr_mesh_topology_create', _addr(indices) or None, self.num_triangles,
+        self.handle = _call(self.lib, 'mesh_topology', 'rdr_mesh_topology_create', _ptr(indices), self.num_triangles,
                             self.num_vertices, int(self.use_gpu), self.gpu_index, on=(use_gpu, gpu_index), ok=bool)
 
     def destroy(self):
@@ -656,22 +655,20 @@ class mesh_topology:
 
     def scratch(self, scheme):
         """floats of (forward scratch, backward scratch, saved) for a weighting scheme (rdr_vertex_normal_scratch)."""
-        counts = [C.c_int64(0) for _ in range(3)]
-        _call(self.lib, 'mesh_topology.scratch', 'rdr_vertex_normal_scratch', self.handle, int(scheme), *[C.byref(c) for c in counts])
-        return tuple(int(c.value) for c in counts)
+        return _outputs(C.c_int64, 3, self.lib, 'mesh_topology.scratch', 'rdr_vertex_normal_scratch', self.handle, int(scheme))
 
 
 def vertex_normal(topology, scheme, vertices, normals, saved, scratch, scratch_floats):
     """Not in the reference's module (its compute_vertex_normal is torch code, pyredner/shape.py): rdr_vertex_normal.  float_ptr
     arguments; writes normals [V, 3] and saved.  Ordered on the current torch stream, not synchronised."""
-    _call(topology.lib, 'vertex_normal', 'rdr_vertex_normal', topology.handle, int(scheme), _addr(vertices), _addr(normals),
-          _addr(saved), _addr(scratch) or None, int(scratch_floats), on=(topology.use_gpu, topology.gpu_index))
+    _call(topology.lib, 'vertex_normal', 'rdr_vertex_normal', topology.handle, int(scheme), _ptr(vertices), _ptr(normals),
+          _ptr(saved), _ptr(scratch), int(scratch_floats), on=(topology.use_gpu, topology.gpu_index))
 
 
 def vertex_normal_backward(topology, scheme, vertices, saved, d_normals, d_vertices, scratch, scratch_floats):
     """Not in the reference's module: rdr_vertex_normal_backward.  Writes every element of d_vertices [V, 3]."""
-    _call(topology.lib, 'vertex_normal_backward', 'rdr_vertex_normal_backward', topology.handle, int(scheme), _addr(vertices),
-          _addr(saved), _addr(d_normals), _addr(d_vertices), _addr(scratch) or None, int(scratch_floats),
+    _call(topology.lib, 'vertex_normal_backward', 'rdr_vertex_normal_backward', topology.handle, int(scheme), _ptr(vertices),
+          _ptr(saved), _ptr(d_normals), _ptr(d_vertices), _ptr(scratch), int(scratch_floats),
           on=(topology.use_gpu, topology.gpu_index))
 
 
@@ -685,45 +682,50 @@ class SmoothWeighting(enum.IntEnum):
 def mesh_smooth_scratch(topology, scheme):
     """Not in the reference's module: floats of (forward scratch, backward scratch, saved) of a smoothing scheme
     (rdr_mesh_smooth_scratch); mesh_smooth needs the forward scratch."""
-    counts = [C.c_int64(0) for _ in range(3)]
-    _call(topology.lib, 'mesh_smooth_scratch', 'rdr_mesh_smooth_scratch', topology.handle, int(scheme), *[C.byref(c) for c in counts])
-    return tuple(int(c.value) for c in counts)
+    return _outputs(C.c_int64, 3, topology.lib, 'mesh_smooth_scratch', 'rdr_mesh_smooth_scratch', topology.handle, int(scheme))
 
 
 def mesh_boundary(topology, bound):
     """Not in the reference's module (its bound_vertices is torch code, pyredner/shape.py): rdr_mesh_boundary.  Writes bound [V]."""
-    _call(topology.lib, 'mesh_boundary', 'rdr_mesh_boundary', topology.handle, _addr(bound), on=(topology.use_gpu, topology.gpu_index))
+    _call(topology.lib, 'mesh_boundary', 'rdr_mesh_boundary', topology.handle, _ptr(bound), on=(topology.use_gpu, topology.gpu_index))
 
 
 def mesh_laplacian(topology, scheme, vertices, control, shift, saved, scratch, scratch_floats):
     """Not in the reference's module (its smooth is torch code, pyredner/shape.py): rdr_mesh_laplacian.  float_ptr arguments;
     control: float_ptr(0) = all 1; writes shift [V, 3] and saved.  Ordered on the current torch stream, not synchronised."""
-    _call(topology.lib, 'mesh_laplacian', 'rdr_mesh_laplacian', topology.handle, int(scheme), _addr(vertices), _addr(control) or None,
-          _addr(shift), _addr(saved), _addr(scratch) or None, int(scratch_floats), on=(topology.use_gpu, topology.gpu_index))
+    _call(topology.lib, 'mesh_laplacian', 'rdr_mesh_laplacian', topology.handle, int(scheme), _ptr(vertices), _ptr(control),
+          _ptr(shift), _ptr(saved), _ptr(scratch), int(scratch_floats), on=(topology.use_gpu, topology.gpu_index))
 
 
 def mesh_laplacian_backward(topology, scheme, vertices, control, saved, d_shift, d_vertices, scratch, scratch_floats):
     """Not in the reference's module: rdr_mesh_laplacian_backward.  Writes every element of d_vertices [V, 3]."""
-    _call(topology.lib, 'mesh_laplacian_backward', 'rdr_mesh_laplacian_backward', topology.handle, int(scheme), _addr(vertices),
-          _addr(control) or None, _addr(saved), _addr(d_shift), _addr(d_vertices), _addr(scratch) or None, int(scratch_floats),
+    _call(topology.lib, 'mesh_laplacian_backward', 'rdr_mesh_laplacian_backward', topology.handle, int(scheme), _ptr(vertices),
+          _ptr(control), _ptr(saved), _ptr(d_shift), _ptr(d_vertices), _ptr(scratch), int(scratch_floats),
           on=(topology.use_gpu, topology.gpu_index))
 
 
 def mesh_smooth(topology, scheme, vertices_in, control, lmd, iterations, vertices_out, scratch, scratch_floats):
     """Not in the reference's module: rdr_mesh_smooth, `iterations` steps vertices + shift * lmd (lmd rounded to fp32).  Writes
     every element of vertices_out [V, 3], which may be vertices_in."""
-    _call(topology.lib, 'mesh_smooth', 'rdr_mesh_smooth', topology.handle, int(scheme), _addr(vertices_in), _addr(control) or None,
-          float(lmd), int(iterations), _addr(vertices_out), _addr(scratch) or None, int(scratch_floats),
+    _call(topology.lib, 'mesh_smooth', 'rdr_mesh_smooth', topology.handle, int(scheme), _ptr(vertices_in), _ptr(control),
+          float(lmd), int(iterations), _ptr(vertices_out), _ptr(scratch), int(scratch_floats),
           on=(topology.use_gpu, topology.gpu_index))
 
 
-def _place(use_gpu, gpu_index):
+def _gpu_index(use_gpu, gpu_index):
     """The gpu_index argument of the C ABI: negative = host memory (the CPU debugging harness only)."""
     return int(gpu_index) if use_gpu else -1
 
 
 def _not_negative(n):
     return n >= 0
+
+
+def _outputs(ctype, n, lib, what, name, *args):
+    """_call with n trailing outputs of `ctype` by reference (the scratch and plan queries) -> their values, a tuple of ints"""
+    out = [ctype(0) for _ in range(n)]
+    _call(lib, what, name, *args, *[C.byref(o) for o in out])
+    return tuple(int(o.value) for o in out)
 
 
 def _call(lib, what, name, *args, on=None, ok=lambda rc: rc == 0):

@@ -27,6 +27,7 @@ from typing import List, Optional
 import torch
 
 from . import redner as _default_backend
+from ._op import place
 
 
 class Camera:
@@ -330,7 +331,7 @@ class RenderFunction(torch.autograd.Function):
         u.area_lights = [rd.AreaLight(lm['shape_id'], fp(T(lm['intensity'])), lm['two_sided'], lm['directly_visible'])
                          for lm in meta['lights']]
         device = meta['device']
-        index = device.index if device.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        use_gpu, index = place(device)
         u.envmap = None
         if meta['envmap'] is not None:
             em = meta['envmap']
@@ -340,7 +341,7 @@ class RenderFunction(torch.autograd.Function):
             u.envmap = rd.EnvironmentMap(values, fp(T(em['env_to_world'])), fp(T(em['world_to_env'])),
                                          fp(T(em['sample_cdf_ys'])), fp(T(em['sample_cdf_xs'])), em['pdf_norm'],
                                          em['directly_visible'])
-        u.scene = rd.Scene(u.camera, u.shapes, u.materials, u.area_lights, u.envmap, device.type == 'cuda', index,
+        u.scene = rd.Scene(u.camera, u.shapes, u.materials, u.area_lights, u.envmap, use_gpu, index,
                            meta['use_primary_edge_sampling'], meta['use_secondary_edge_sampling'])
         u.options = rd.RenderOptions(seed[0], meta['num_samples'][0], meta['max_bounces'], meta['channels'],
                                      meta['sampler_type'], meta['sample_pixel_center'])

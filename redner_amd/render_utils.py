@@ -29,6 +29,7 @@ from typing import List, Optional, Union
 import torch
 
 from . import redner as _default_backend
+from ._op import place, ptr, upstream
 from .render_pytorch import RenderFunction, Scene
 
 _LIGHT_PARAMS = 10          # csrc/deferred.h: intensity 3, position 3, direction 3, spot exponent 1
@@ -157,14 +158,13 @@ class DeferredShade(torch.autograd.Function):
         if g_buffer.dtype != torch.float32 or light_params.dtype != torch.float32:
             raise RuntimeError('DeferredShade: fp32 tensors only')
         device = g_buffer.device
-        use_gpu = device.type == 'cuda'
-        index = device.index if device.index is not None else (torch.cuda.current_device() if use_gpu else 0)
+        use_gpu, index = place(device)
         g = _aligned(g_buffer.detach(), alpha)
         params = light_params.detach().to(device).contiguous()
         h, w = hg // aa_samples, wg // aa_samples
         image = torch.empty(n, h, w, 3 + int(alpha), dtype=torch.float32, device=device)
         geometry = (n, h, w, aa_samples, alpha, light_types, image_light_ranges, use_gpu, index)
-        rd.deferred_shade(rd.float_ptr(g.data_ptr()), rd.float_ptr(params.data_ptr()), rd.float_ptr(image.data_ptr()), *geometry)
+        rd.deferred_shade(ptr(rd, g), ptr(rd, params), ptr(rd, image), *geometry)
         ctx.rd, ctx.geometry, ctx.params_device = rd, geometry, light_params.device
         ctx.save_for_backward(g, params)
         return image
@@ -174,12 +174,11 @@ class DeferredShade(torch.autograd.Function):
         rd, geometry = ctx.rd, ctx.geometry
         g, params = ctx.saved_tensors
         alpha = geometry[4]
-        grad_img = _aligned(grad_img.to(g.device, torch.float32), alpha)
+        grad_img = _aligned(upstream(grad_img, g.device), alpha)
         assert torch.isfinite(grad_img).all()
         d_g = torch.empty_like(g)
         d_params = torch.empty_like(params)
-        rd.deferred_shade_backward(rd.float_ptr(g.data_ptr()), rd.float_ptr(params.data_ptr()), rd.float_ptr(grad_img.data_ptr()),
-                                   rd.float_ptr(d_g.data_ptr()), rd.float_ptr(d_params.data_ptr()), *geometry)
+        rd.deferred_shade_backward(ptr(rd, g), ptr(rd, params), ptr(rd, grad_img), ptr(rd, d_g), ptr(rd, d_params), *geometry)
         return d_g, d_params.to(ctx.params_device), None, None, None, None, None
 
 

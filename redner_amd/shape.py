@@ -28,15 +28,10 @@ import threading
 import torch
 
 from . import redner as _default_backend
+from ._op import place, ptr, scratch, upstream
 
 SCHEMES = {'max': 0, 'cotangent': 1}
 PLAN_CACHE_SIZE = 8
-
-
-def _place(t):
-    use_gpu = t.device.type == 'cuda'
-    index = t.device.index if t.device.index is not None else (torch.cuda.current_device() if use_gpu else 0)
-    return use_gpu, index
 
 
 class MeshTopology:
@@ -55,8 +50,7 @@ class MeshTopology:
             raise RuntimeError('MeshTopology: int32 or int64 indices only')
         indices = indices.detach().contiguous()
         self.num_vertices, self.num_triangles, self.device = int(num_vertices), int(indices.shape[0]), indices.device
-        use_gpu, index = _place(indices)
-        self.native = rd.mesh_topology(rd.int_ptr(indices.data_ptr()), self.num_triangles, self.num_vertices, use_gpu, index)
+        self.native = rd.mesh_topology(rd.int_ptr(indices.data_ptr()), self.num_triangles, self.num_vertices, *place(indices))
         self.rd = rd
 
     def rows(self):
@@ -80,9 +74,8 @@ class VertexNormals(torch.autograd.Function):
         n_fwd, _, n_saved = topology.native.scratch(scheme)
         normals = torch.empty_like(v)
         saved = torch.empty(max(n_saved, 1), dtype=torch.float32, device=v.device)
-        scratch = torch.empty(max(n_fwd, 1), dtype=torch.float32, device=v.device)
-        rd.vertex_normal(topology.native, scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(normals.data_ptr()),
-                         rd.float_ptr(saved.data_ptr()), rd.float_ptr(scratch.data_ptr()), n_fwd)
+        work = scratch(n_fwd, v.device)
+        rd.vertex_normal(topology.native, scheme, ptr(rd, v), ptr(rd, normals), ptr(rd, saved), ptr(rd, work), n_fwd)
         ctx.topology, ctx.scheme = topology, scheme
         ctx.save_for_backward(v, saved)
         ctx.set_materialize_grads(False)
@@ -94,13 +87,12 @@ class VertexNormals(torch.autograd.Function):
             return None, None, None
         topology, rd = ctx.topology, ctx.topology.rd
         v, saved = ctx.saved_tensors
-        g = d_normals.to(device=v.device, dtype=torch.float32).contiguous()
+        g = upstream(d_normals, v.device)
         n_bwd = topology.native.scratch(ctx.scheme)[1]
         d_vertices = torch.empty_like(v)
-        scratch = torch.empty(max(n_bwd, 1), dtype=torch.float32, device=v.device)
-        rd.vertex_normal_backward(topology.native, ctx.scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(saved.data_ptr()),
-                                  rd.float_ptr(g.data_ptr()), rd.float_ptr(d_vertices.data_ptr()), rd.float_ptr(scratch.data_ptr()),
-                                  n_bwd)
+        work = scratch(n_bwd, v.device)
+        rd.vertex_normal_backward(topology.native, ctx.scheme, ptr(rd, v), ptr(rd, saved), ptr(rd, g), ptr(rd, d_vertices),
+                                  ptr(rd, work), n_bwd)
         return d_vertices, None, None
 
 
@@ -175,7 +167,7 @@ def _smooth_arguments(who, vertices, indices, weighting_scheme, topology, backen
 def _boundary(topology):
     rd = topology.rd
     bound = torch.empty(topology.num_vertices, dtype=torch.float32, device=topology.device)
-    rd.mesh_boundary(topology.native, rd.float_ptr(bound.data_ptr()))
+    rd.mesh_boundary(topology.native, ptr(rd, bound))
     return bound
 
 
@@ -204,9 +196,8 @@ class MeshLaplacian(torch.autograd.Function):
         n_fwd, _, n_saved = rd.mesh_smooth_scratch(topology.native, scheme)
         shift = torch.empty_like(v)
         saved = torch.empty(max(n_saved, 1), dtype=torch.float32, device=v.device)
-        scratch = torch.empty(max(n_fwd, 1), dtype=torch.float32, device=v.device)
-        rd.mesh_laplacian(topology.native, scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(control.data_ptr()),
-                          rd.float_ptr(shift.data_ptr()), rd.float_ptr(saved.data_ptr()), rd.float_ptr(scratch.data_ptr()), n_fwd)
+        work = scratch(n_fwd, v.device)
+        rd.mesh_laplacian(topology.native, scheme, ptr(rd, v), ptr(rd, control), ptr(rd, shift), ptr(rd, saved), ptr(rd, work), n_fwd)
         ctx.topology, ctx.scheme = topology, scheme
         ctx.save_for_backward(v, control, saved)
         ctx.set_materialize_grads(False)
@@ -218,13 +209,12 @@ class MeshLaplacian(torch.autograd.Function):
             return None, None, None, None
         topology, rd = ctx.topology, ctx.topology.rd
         v, control, saved = ctx.saved_tensors
-        g = d_shift.to(device=v.device, dtype=torch.float32).contiguous()
+        g = upstream(d_shift, v.device)
         n_bwd = rd.mesh_smooth_scratch(topology.native, ctx.scheme)[1]
         d_vertices = torch.empty_like(v)
-        scratch = torch.empty(max(n_bwd, 1), dtype=torch.float32, device=v.device)
-        rd.mesh_laplacian_backward(topology.native, ctx.scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(control.data_ptr()),
-                                   rd.float_ptr(saved.data_ptr()), rd.float_ptr(g.data_ptr()), rd.float_ptr(d_vertices.data_ptr()),
-                                   rd.float_ptr(scratch.data_ptr()), n_bwd)
+        work = scratch(n_bwd, v.device)
+        rd.mesh_laplacian_backward(topology.native, ctx.scheme, ptr(rd, v), ptr(rd, control), ptr(rd, saved), ptr(rd, g),
+                                   ptr(rd, d_vertices), ptr(rd, work), n_bwd)
         return d_vertices, None, None, None
 
 
@@ -250,8 +240,8 @@ def smooth(vertices, indices, lmd, weighting_scheme='reciprocal', control=None, 
     v = vertices.detach().contiguous()
     n_fwd = rd.mesh_smooth_scratch(topology.native, scheme)[0]
     moved = torch.empty_like(v)
-    scratch = torch.empty(max(n_fwd, 1), dtype=torch.float32, device=v.device)
-    rd.mesh_smooth(topology.native, scheme, rd.float_ptr(v.data_ptr()), rd.float_ptr(control.data_ptr()), float(lmd), int(iterations),
-                   rd.float_ptr(moved.data_ptr()), rd.float_ptr(scratch.data_ptr()), n_fwd)
+    work = scratch(n_fwd, v.device)
+    rd.mesh_smooth(topology.native, scheme, ptr(rd, v), ptr(rd, control), float(lmd), int(iterations), ptr(rd, moved), ptr(rd, work),
+                   n_fwd)
     with torch.no_grad():
         vertices.copy_(moved)              # (not a write through .data: that would leave vertices._version where it was)

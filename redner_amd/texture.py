@@ -33,6 +33,7 @@ import torch
 
 from . import redner as _default_backend
 from . import render_pytorch
+from ._op import named, place, ptr, scratch, upstream
 
 
 def _level_sizes(height, width, num_levels):
@@ -41,12 +42,6 @@ def _level_sizes(height, width, num_levels):
         height, width = max(height // 2, 1), max(width // 2, 1)
         sizes.append((height, width))
     return sizes
-
-
-def _place(t):
-    use_gpu = t.device.type == 'cuda'
-    index = t.device.index if t.device.index is not None else (torch.cuda.current_device() if use_gpu else 0)
-    return use_gpu, index
 
 
 class MipPyramid(torch.autograd.Function):
@@ -66,8 +61,8 @@ class MipPyramid(torch.autograd.Function):
         if len(sizes) < 2:
             raise RuntimeError('MipPyramid: a 1 x 1 image has no further levels')
         levels = [base] + [torch.empty(hl, wl, c, dtype=torch.float32, device=base.device) for hl, wl in sizes[1:]]
-        use_gpu, index = _place(base)
-        rd.mip_pyramid([rd.float_ptr(l.data_ptr()) for l in levels], h, w, c, use_gpu, index)
+        use_gpu, index = place(base)
+        rd.mip_pyramid([ptr(rd, l) for l in levels], h, w, c, use_gpu, index)
         ctx.rd, ctx.geometry, ctx.device = rd, (h, w, c, use_gpu, index), base.device
         ctx.set_materialize_grads(False)
         return tuple(levels[1:])
@@ -76,13 +71,11 @@ class MipPyramid(torch.autograd.Function):
     def backward(ctx, *d_levels):
         rd = ctx.rd
         h, w, c, use_gpu, index = ctx.geometry
-        grads = [None if g is None else g.to(device=ctx.device, dtype=torch.float32).contiguous() for g in d_levels]
         d_texels = torch.empty(h, w, c, dtype=torch.float32, device=ctx.device)
         count = rd.mip_backward_scratch(h, w, c)
-        scratch = torch.empty(max(count, 1), dtype=torch.float32, device=ctx.device)
-        ptrs = [rd.float_ptr(0)] + [rd.float_ptr(0 if g is None else g.data_ptr()) for g in grads]       # g_0: autograd adds it
-        rd.mip_pyramid_backward(ptrs, rd.float_ptr(d_texels.data_ptr()), rd.float_ptr(scratch.data_ptr()), count, h, w, c,
-                                use_gpu, index)
+        work = scratch(count, ctx.device)
+        grads = [None] + [upstream(g, ctx.device) for g in d_levels]                                     # g_0: autograd adds it
+        rd.mip_pyramid_backward([ptr(rd, g) for g in grads], ptr(rd, d_texels), ptr(rd, work), count, h, w, c, use_gpu, index)
         return d_texels, None
 
 
@@ -177,15 +170,12 @@ def envmap_sampling_tables(texels, backend=None):
         raise RuntimeError('envmap_sampling_tables: fp32 texels only')
     base = texels.detach().contiguous()
     h, w = int(base.shape[0]), int(base.shape[1])
-    use_gpu, index = _place(base)
+    use_gpu, index = place(base)
     y_weight = _y_weight(h, base.device)
     cdf_ys = torch.empty(h, dtype=torch.float32, device=base.device)
     cdf_xs = torch.empty(h, w, dtype=torch.float32, device=base.device)
-    try:
-        total = rd.envmap_tables(rd.float_ptr(base.data_ptr()), rd.float_ptr(y_weight.data_ptr()), rd.float_ptr(cdf_ys.data_ptr()),
-                                 rd.float_ptr(cdf_xs.data_ptr()), h, w, use_gpu, index)
-    except RuntimeError as e:
-        raise RuntimeError('envmap_sampling_tables: %s' % e) from e
+    with named('envmap_sampling_tables'):
+        total = rd.envmap_tables(ptr(rd, base), ptr(rd, y_weight), ptr(rd, cdf_ys), ptr(rd, cdf_xs), h, w, use_gpu, index)
     pdf_norm = (h * w) / (total * (2 * math.pi * math.pi))
     return cdf_ys, cdf_xs, pdf_norm
 

@@ -21,14 +21,9 @@ translation and centre are read on the device.
 import torch
 
 from . import redner as _default_backend
+from ._op import named, place, ptr, scratch, upstream
 
 MAX_SETS = 16
-
-
-def _place(t):
-    use_gpu = t.device.type == 'cuda'
-    index = t.device.index if t.device.index is not None else (torch.cuda.current_device() if use_gpu else 0)
-    return use_gpu, index
 
 
 class RotateMatrix(torch.autograd.Function):
@@ -38,36 +33,32 @@ class RotateMatrix(torch.autograd.Function):
     def forward(ctx, angles, backend=None):
         rd = backend or _default_backend
         a = angles.detach().contiguous()
-        use_gpu, index = _place(a)
         matrix = torch.empty(3, 3, dtype=torch.float32, device=a.device)
-        rd.rotate_matrix(rd.float_ptr(a.data_ptr()), rd.float_ptr(matrix.data_ptr()), use_gpu, index)
+        rd.rotate_matrix(ptr(rd, a), ptr(rd, matrix), *place(a))
         ctx.rd, ctx.angles = rd, a
         return matrix
 
     @staticmethod
     def backward(ctx, d_matrix):
         rd, a = ctx.rd, ctx.angles
-        use_gpu, index = _place(a)
-        g = d_matrix.to(device=a.device, dtype=torch.float32).contiguous()
+        g = upstream(d_matrix, a.device)
         d_angles = torch.empty(3, dtype=torch.float32, device=a.device)
-        rd.rotate_matrix_backward(rd.float_ptr(a.data_ptr()), rd.float_ptr(g.data_ptr()), rd.float_ptr(d_angles.data_ptr()), use_gpu, index)
+        rd.rotate_matrix_backward(ptr(rd, a), ptr(rd, g), ptr(rd, d_angles), *place(a))
         return d_angles, None
 
 
 def _forward(rd, sets, a, t, c):
     """sets, a, t, c (or None): detached contiguous fp32 on one device.  -> the posed sets, saved [12] (R, then the centre used)"""
     device = sets[0].device
-    use_gpu, index = _place(sets[0])
     counts = [int(v.shape[0]) for v in sets]
     out = [torch.empty_like(v) for v in sets]
     saved = torch.empty(12, dtype=torch.float32, device=device)
-    scratch, floats = None, 0
+    work, floats = None, 0
     if c is None:
         floats, _ = rd.pose_scratch(counts)
-        scratch = torch.empty((floats + 1) // 2, dtype=torch.float64, device=device)
-    ptr = (lambda x: None if x is None else rd.float_ptr(x.data_ptr()))
-    rd.pose_vertices([ptr(v) for v in sets], counts, ptr(a), ptr(t), ptr(c), [ptr(o) for o in out], ptr(saved), ptr(scratch), floats,
-                     use_gpu, index)
+        work = scratch(floats, device)
+    rd.pose_vertices([ptr(rd, v) for v in sets], counts, ptr(rd, a), ptr(rd, t), ptr(rd, c), [ptr(rd, o) for o in out],
+                     ptr(rd, saved), ptr(rd, work), floats, *place(device))
     return out, saved
 
 
@@ -91,17 +82,15 @@ class PoseVertices(torch.autograd.Function):
     def backward(ctx, *d_out):
         rd, sets, counts, a = ctx.rd, ctx.sets, ctx.counts, ctx.angles
         device = sets[0].device
-        use_gpu, index = _place(sets[0])
-        g = [None if d is None else d.to(device=device, dtype=torch.float32).contiguous() for d in d_out]
+        g = [upstream(d, device) for d in d_out]
         d_vertices = [torch.empty_like(v) if ctx.needs_input_grad[4 + k] else None for k, v in enumerate(sets)]
         d_angles, d_translation = (torch.empty(3, dtype=torch.float32, device=device) for _ in range(2))
         d_center = None if ctx.own else torch.empty(3, dtype=torch.float32, device=device)
         _, floats = rd.pose_scratch(counts)
-        scratch = torch.empty((floats + 1) // 2, dtype=torch.float64, device=device)
-        ptr = (lambda x: None if x is None else rd.float_ptr(x.data_ptr()))
-        rd.pose_vertices_backward([ptr(v) for v in sets], counts, ptr(a), ptr(ctx.saved), ctx.own, [ptr(d) for d in g],
-                                  [ptr(d) for d in d_vertices] if any(d is not None for d in d_vertices) else None,
-                                  ptr(d_angles), ptr(d_translation), ptr(d_center), ptr(scratch), floats, use_gpu, index)
+        work = scratch(floats, device)
+        rd.pose_vertices_backward([ptr(rd, v) for v in sets], counts, ptr(rd, a), ptr(rd, ctx.saved), ctx.own, [ptr(rd, d) for d in g],
+                                  [ptr(rd, d) for d in d_vertices] if any(d is not None for d in d_vertices) else None,
+                                  ptr(rd, d_angles), ptr(rd, d_translation), ptr(rd, d_center), ptr(rd, work), floats, *place(device))
         return (d_angles, d_translation, d_center, None) + tuple(d_vertices)
 
 
@@ -124,10 +113,8 @@ def gen_rotate_matrix(angles, backend=None):
         angles = _triple(who, 'angles', angles, angles.device)
     else:
         raise ValueError('%s: angles must be a tensor of shape [3]' % who)
-    try:
+    with named(who):
         return RotateMatrix.apply(angles, backend)
-    except RuntimeError as e:
-        raise RuntimeError('%s: %s' % (who, e)) from e
 
 
 def _checked(who, vertices, angles, translation, center):
@@ -162,9 +149,7 @@ def pose_vertices(vertices, angles, translation, center=None, backend=None):
     they live)."""
     who = 'pose_vertices'
     single, sets, angles, translation, center = _checked(who, vertices, angles, translation, center)
-    try:
+    with named(who):
         out = PoseVertices.apply(angles, translation, center, backend, *sets)
-    except RuntimeError as e:
-        raise RuntimeError('%s: %s' % (who, e)) from e
     return out[0] if single else (tuple(out) if isinstance(vertices, tuple) else list(out))
 

@@ -18,12 +18,7 @@ CPU tensors are accepted by the CPU debugging harness only (the test-suite loads
 import torch
 
 from . import redner as _default_backend
-
-
-def _place(t):
-    use_gpu = t.device.type == 'cuda'
-    index = t.device.index if t.device.index is not None else (torch.cuda.current_device() if use_gpu else 0)
-    return use_gpu, index
+from ._op import named, place, ptr, scratch, upstream
 
 
 class SHReconstruct(torch.autograd.Function):
@@ -34,11 +29,11 @@ class SHReconstruct(torch.autograd.Function):
         rd = backend or _default_backend
         base = coeffs.detach().contiguous()
         channels, num_coeffs = (int(v) for v in base.shape)
-        use_gpu, index = _place(base)
+        use_gpu, index = place(base)
         image = torch.empty(height, width, channels, dtype=torch.float32, device=base.device)
         clamp = torch.empty(height, width, channels, dtype=torch.uint8, device=base.device) if ctx.needs_input_grad[0] else None
-        rd.sh_reconstruct(rd.float_ptr(base.data_ptr()), rd.float_ptr(image.data_ptr()), None if clamp is None else clamp.data_ptr(),
-                          channels, num_coeffs, height, width, use_gpu, index)
+        rd.sh_reconstruct(ptr(rd, base), ptr(rd, image), None if clamp is None else clamp.data_ptr(), channels, num_coeffs, height,
+                          width, use_gpu, index)
         ctx.rd, ctx.geometry, ctx.clamp = rd, (channels, num_coeffs, height, width, use_gpu, index), clamp
         return image
 
@@ -47,12 +42,12 @@ class SHReconstruct(torch.autograd.Function):
         rd = ctx.rd
         channels, num_coeffs, height, width, use_gpu, index = ctx.geometry
         clamp = ctx.clamp
-        g = d_image.to(device=clamp.device, dtype=torch.float32).contiguous()
+        g = upstream(d_image, clamp.device)
         d_coeffs = torch.empty(channels, num_coeffs, dtype=torch.float32, device=clamp.device)
         count = rd.sh_backward_scratch(height, width, channels, num_coeffs)
-        scratch = torch.empty(max(count // 2, 1), dtype=torch.float64, device=clamp.device)
-        rd.sh_reconstruct_backward(clamp.data_ptr(), rd.float_ptr(g.data_ptr()), rd.float_ptr(d_coeffs.data_ptr()),
-                                   rd.float_ptr(scratch.data_ptr()), count, channels, num_coeffs, height, width, use_gpu, index)
+        work = scratch(count, clamp.device)
+        rd.sh_reconstruct_backward(clamp.data_ptr(), ptr(rd, g), ptr(rd, d_coeffs), ptr(rd, work), count, channels, num_coeffs, height,
+                                   width, use_gpu, index)
         return d_coeffs, None, None, None
 
 
@@ -65,7 +60,5 @@ def SH_reconstruct(coeffs, res, backend=None):
         raise ValueError('SH_reconstruct: fp32 coeffs only, got %s' % (coeffs.dtype,))
     if len(res) != 2 or int(res[0]) <= 0 or int(res[1]) <= 0:
         raise ValueError('SH_reconstruct: res must be (height, width), both positive, got %s' % (tuple(res),))
-    try:
+    with named('SH_reconstruct'):
         return SHReconstruct.apply(coeffs, int(res[0]), int(res[1]), backend)
-    except RuntimeError as e:
-        raise RuntimeError('SH_reconstruct: %s' % e) from e

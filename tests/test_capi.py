@@ -62,9 +62,9 @@ def test_missing_library_is_an_error(tmp_path):
         _capi.load(str(tmp_path / 'nope.so'))
 
 
-def declared_signatures():
-    """name -> number of parameters, for every rdr_* function include/redner_amd.h declares"""
-    src = open(HEADER).read()
+def declared_signatures(header):
+    """name -> number of parameters, for every rdr_* function the header of include/ declares"""
+    src = open(os.path.join(ROOT, 'include', header)).read()
     src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
     src = re.sub(r'//[^\n]*', '', src)
     found = {}
@@ -74,16 +74,39 @@ def declared_signatures():
     return found
 
 
-def test_signature_table_matches_the_header():
-    """Every declared function has a (restype, argtypes) entry of the right length and there is no entry without a declaration: a
-    forgotten signature would send 64-bit handles through ctypes' default int conversion."""
+# header -> what pins its set of functions: how many there are (redner_amd.h, which is fixed) or their sorted names
+DECLARED = {
+    'redner_amd.h': 43,
+    'redner_amd_mesh.h': ['rdr_mesh_boundary', 'rdr_mesh_laplacian', 'rdr_mesh_laplacian_backward', 'rdr_mesh_smooth',
+                          'rdr_mesh_smooth_scratch'],
+    'redner_amd_image.h': ['rdr_pyramid_loss', 'rdr_pyramid_loss_backward', 'rdr_pyramid_loss_plan', 'rdr_pyramid_loss_scratch'],
+    'redner_amd_pose.h': ['rdr_pose_plan', 'rdr_pose_scratch', 'rdr_pose_vertices', 'rdr_pose_vertices_backward',
+                          'rdr_rotate_matrix', 'rdr_rotate_matrix_backward'],
+    'redner_amd_debug.h': ['rdr_debug_lane_park'],
+}
+
+
+@pytest.mark.parametrize('header', list(DECLARED))
+def test_signature_table_matches_the_header(hostsim_backend, header):
+    """Every function a header declares has a (restype, argtypes) entry of the right length under that header in _capi.HEADERS and
+    there is no entry without a declaration: a forgotten signature would send 64-bit handles through ctypes' default int
+    conversion.  No name stands under two headers, and the harness library and, where they are built, both product libraries
+    export every one."""
+    from conftest import HOSTSIM_LIB
     from redner_amd import _capi
-    declared = declared_signatures()
-    assert len(declared) == 43
-    assert set(declared) == set(_capi.SIGNATURES) == set(_capi.EXPORTS)
+    declared, table, pinned = declared_signatures(header), _capi.HEADERS[header], DECLARED[header]
+    assert sorted(_capi.HEADERS) == sorted(DECLARED) == sorted(os.listdir(os.path.join(ROOT, 'include')))
+    assert (len(declared) if isinstance(pinned, int) else sorted(declared)) == pinned
+    assert set(declared) == set(table)
     for name, count in declared.items():
-        restype, argtypes = _capi.SIGNATURES[name]
-        assert len(argtypes) == count, name
+        assert len(table[name][1]) == count, name
+    for other, others in _capi.HEADERS.items():
+        assert other == header or not set(declared) & set(others), other
+    for path in (HOSTSIM_LIB, _capi.DEFAULT_LIBRARY, _capi.EXACT_LIBRARY):
+        if path == HOSTSIM_LIB or os.path.exists(path):
+            lib = ctypes.CDLL(path)
+            for name in declared:
+                assert hasattr(lib, name), (path, name)
 
 
 def _null_handles_are_errors(lib, tmp_path):

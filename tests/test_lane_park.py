@@ -13,7 +13,6 @@ on the CPU harness.
    parity_util's bars."""
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -82,20 +81,6 @@ def test_probe_rejects_bad_arguments(hostsim_backend):
     assert 'rdr_debug_lane_park' in K.last_error()
     assert lib.rdr_debug_lane_park(4, None, None, None, ctypes.byref(cols)) == 1
     assert lib.rdr_debug_lane_park(0, None, None, None, None) == 1
-
-
-def test_debug_header_matches_the_signature_table(hostsim_backend):
-    """What tests/test_capi.py holds redner_amd.h and _capi.SIGNATURES to, for include/redner_amd_debug.h and
-    _capi.DEBUG_SIGNATURES: the same names, argument counts that agree, no name in another table, every function exported."""
-    from conftest import ROOT
-    src = open(os.path.join(ROOT, 'include', 'redner_amd_debug.h')).read()
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', src, flags=re.S))
-    declared = {name: len(params.split(',')) for name, params in re.findall(r'\b(rdr_[a-z_0-9]+)\s*\(([^()]*)\)\s*;', src)}
-    assert set(declared) == set(K.DEBUG_SIGNATURES) and declared
-    assert not set(declared) & (set(K.SIGNATURES) | set(K.MESH_SIGNATURES) | set(K.IMAGE_SIGNATURES))
-    for name, count in declared.items():
-        assert len(K.DEBUG_SIGNATURES[name][1]) == count, name
-        assert hasattr(K.lib(), name)
 
 
 # ---- renders with partial waves / partial workgroups -------------------------------------------------------------------------------

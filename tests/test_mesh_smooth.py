@@ -478,30 +478,3 @@ def test_exports(hostsim_backend):
     assert redner_amd.bound_vertices is sm.bound_vertices and redner_amd.MeshLaplacian is sm.MeshLaplacian
     assert redner_amd.bound_vertices(vertices, indices, backend=hostsim_backend).tolist() == [1.0, 0.0, 0.0, 0.0, 0.0, 0.0]
     assert int(hostsim_backend.SmoothWeighting.cotangent) == sm.SMOOTH_SCHEMES['cotangent'] == 2
-
-
-# ---- 5. the C boundary ----------------------------------------------------------------------------------------------------------
-def _declared_mesh_signatures():
-    """name -> number of parameters, for every rdr_* function include/redner_amd_mesh.h declares"""
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, 'include', 'redner_amd_mesh.h')).read()
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', src, flags=re.S))
-    return {name: len(params.split(',')) for name, params in re.findall(r'\b(rdr_[a-z_0-9]+)\s*\(([^()]*)\)\s*;', src)}
-
-
-def test_mesh_signature_table_matches_its_header(hostsim_backend):
-    """What tests/test_capi.py holds redner_amd.h and _capi.SIGNATURES to, for the companion header and _capi.MESH_SIGNATURES:
-    the same names, argument counts that agree, no name in both tables, every function exported by the harness library and,
-    where it is built, by the product library."""
-    from redner_amd import _capi
-    declared = _declared_mesh_signatures()
-    assert sorted(declared) == ['rdr_mesh_boundary', 'rdr_mesh_laplacian', 'rdr_mesh_laplacian_backward', 'rdr_mesh_smooth',
-                                'rdr_mesh_smooth_scratch']
-    assert set(declared) == set(_capi.MESH_SIGNATURES) and not set(declared) & set(_capi.SIGNATURES)
-    for name, count in declared.items():
-        assert len(_capi.MESH_SIGNATURES[name][1]) == count, name
-    libraries = [_capi.lib()] + [ctypes.CDLL(p) for p in (_capi.DEFAULT_LIBRARY, _capi.EXACT_LIBRARY) if os.path.exists(p)]
-    for lib in libraries:
-        for name in declared:
-            assert hasattr(lib, name), name

@@ -13,9 +13,7 @@ Bars
     gen_rotate_matrix is the R pose_vertices used; d_translation of integer-valued upstream gradients is their exact column sum.
   * the adjoint identity, test_adjoint_identity_*: see its docstring.
 The harness cases run the same per-vertex and per-chunk bodies as the kernels, as plain loops; the GPU cases run on both builds."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -475,33 +473,6 @@ def test_errors_gpu(gpu_backend):
         pose_vertices(torch.zeros(5, 3), torch.zeros(3), torch.zeros(3), backend=gpu_backend)
     with pytest.raises(RuntimeError, match='gen_rotate_matrix.*harness'):
         gen_rotate_matrix(torch.zeros(3), backend=gpu_backend)
-
-
-# ---- 8. the C boundary ----------------------------------------------------------------------------------------------------------
-def _declared_pose_signatures():
-    """name -> number of parameters, for every rdr_* function include/redner_amd_pose.h declares"""
-    src = open(os.path.join(ROOT, 'include', 'redner_amd_pose.h')).read()
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', src, flags=re.S))
-    return {name: len(params.split(',')) for name, params in re.findall(r'\b(rdr_[a-z_0-9]+)\s*\(([^()]*)\)\s*;', src)}
-
-
-def test_pose_signature_table_matches_its_header(hostsim_backend):
-    """What tests/test_pyramid_loss.py holds redner_amd_image.h and _capi.IMAGE_SIGNATURES to, for redner_amd_pose.h and
-    _capi.POSE_SIGNATURES: the same names, argument counts that agree, no name in another table, every function exported by the
-    harness library and, where it is built, by the product library."""
-    from redner_amd import _capi
-    declared = _declared_pose_signatures()
-    assert sorted(declared) == ['rdr_pose_plan', 'rdr_pose_scratch', 'rdr_pose_vertices', 'rdr_pose_vertices_backward',
-                                'rdr_rotate_matrix', 'rdr_rotate_matrix_backward']
-    assert set(declared) == set(_capi.POSE_SIGNATURES)
-    others = set(_capi.SIGNATURES) | set(_capi.MESH_SIGNATURES) | set(_capi.IMAGE_SIGNATURES) | set(_capi.DEBUG_SIGNATURES)
-    assert not set(declared) & others
-    for name, count in declared.items():
-        assert len(_capi.POSE_SIGNATURES[name][1]) == count, name
-    libraries = [_capi.lib()] + [ctypes.CDLL(p) for p in (_capi.DEFAULT_LIBRARY, _capi.EXACT_LIBRARY) if os.path.exists(p)]
-    for lib in libraries:
-        for name in declared:
-            assert hasattr(lib, name), name
 
 
 # ---- 10. end to end: the pose, a render, the loss, the gradients of angles and translation ------------------------------------------

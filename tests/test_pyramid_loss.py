@@ -30,10 +30,8 @@ Bars
   * adjoint identity: <A^T A x, y> == <A x, A y> to 1e-5 relative, fp64 accumulation, per level.
   * clamp ties: at D = +-c the gradient is bit for bit the one of the unclamped op on the clamped difference; beyond, exactly 0.
 The harness cases run the same per-texel bodies as the kernels, as plain loops; the GPU cases run on both builds."""
-import ctypes
 import hashlib
 import os
-import re
 
 import numpy as np
 import pytest
@@ -400,31 +398,6 @@ def test_errors_gpu(gpu_backend):
     # no torch fall-back and no silent CPU path: CPU tensors are for the harness library only
     with pytest.raises(RuntimeError, match='gaussian_pyramid_loss.*harness'):
         gaussian_pyramid_loss(torch.zeros(8, 8, 3), torch.zeros(8, 8, 3), 2, backend=gpu_backend)
-
-
-# ---- 8. the C boundary ----------------------------------------------------------------------------------------------------------
-def _declared_image_signatures():
-    """name -> number of parameters, for every rdr_* function include/redner_amd_image.h declares"""
-    src = open(os.path.join(ROOT, 'include', 'redner_amd_image.h')).read()
-    src = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', src, flags=re.S))
-    return {name: len(params.split(',')) for name, params in re.findall(r'\b(rdr_[a-z_0-9]+)\s*\(([^()]*)\)\s*;', src)}
-
-
-def test_image_signature_table_matches_its_header(hostsim_backend):
-    """What tests/test_mesh_smooth.py holds redner_amd_mesh.h and _capi.MESH_SIGNATURES to, for redner_amd_image.h and
-    _capi.IMAGE_SIGNATURES: the same names, argument counts that agree, no name in another table, every function exported by the
-    harness library and, where it is built, by the product library."""
-    from redner_amd import _capi
-    declared = _declared_image_signatures()
-    assert sorted(declared) == ['rdr_pyramid_loss', 'rdr_pyramid_loss_backward', 'rdr_pyramid_loss_plan', 'rdr_pyramid_loss_scratch']
-    assert set(declared) == set(_capi.IMAGE_SIGNATURES)
-    assert not set(declared) & set(_capi.SIGNATURES) and not set(declared) & set(_capi.MESH_SIGNATURES)
-    for name, count in declared.items():
-        assert len(_capi.IMAGE_SIGNATURES[name][1]) == count, name
-    libraries = [_capi.lib()] + [ctypes.CDLL(p) for p in (_capi.DEFAULT_LIBRARY, _capi.EXACT_LIBRARY) if os.path.exists(p)]
-    for lib in libraries:
-        for name in declared:
-            assert hasattr(lib, name), name
 
 
 # ---- 9. end to end: a render, the loss, the vertex gradient ----------------------------------------------------------------------

@@ -23,9 +23,10 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools')]
 
 from redner_amd import render_utils as ru          # noqa: E402
+from op_bench import emit, require_gpu, time_alternating          # noqa: E402
 
 AA = 2
 PEAK_BYTES_PER_S = 8.0e12
@@ -101,27 +102,6 @@ def clear_grads(spec, *tensors):
         t.grad = None
 
 
-def time_alternating(base, fused, iters, warmup):
-    for _ in range(warmup):
-        base()
-        fused()
-    torch.cuda.synchronize()
-    times = {'torch': [], 'fused': []}
-    for _ in range(iters):
-        for name, f in (('torch', base), ('fused', fused)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1))
-    out = {}
-    for name, ts in times.items():
-        ts = sorted(ts)
-        out[name] = {'median_ms': ts[len(ts) // 2], 'p10_ms': ts[len(ts) // 10], 'p90_ms': ts[(len(ts) * 9) // 10]}
-    return out
-
-
 def algorithmic_bytes(size, num_lights):
     texels, pixels = (size * AA) ** 2, size * size
     blocks = min((pixels + 255) // 256, 2048)
@@ -152,8 +132,8 @@ def shade_cases(size, device, iters, warmup):
         ru.deferred_shade(g.unsqueeze(0), lights, alpha=True, aa_samples=AA)[0].backward(up)
 
     return {'max_abs_difference_of_images': err,
-            'a_shade_forward': time_alternating(fwd_torch, fwd_fused, iters, warmup),
-            'b_shade_forward_backward': time_alternating(both_torch, both_fused, iters, warmup)}
+            'a_shade_forward': time_alternating({'torch': fwd_torch, 'fused': fwd_fused}, iters, warmup),
+            'b_shade_forward_backward': time_alternating({'torch': both_torch, 'fused': both_fused}, iters, warmup)}
 
 
 def whole_iteration_case(size, device, iters, warmup):
@@ -174,7 +154,7 @@ def whole_iteration_case(size, device, iters, warmup):
         clear_grads(spec, *leaves)
         ru.render_deferred(sc, lights, alpha=True, aa_samples=AA, seed=1, device=device).backward(up)
 
-    return {'c_render_deferred_forward_backward': time_alternating(it_torch, it_fused, iters, warmup)}
+    return {'c_render_deferred_forward_backward': time_alternating({'torch': it_torch, 'fused': it_fused}, iters, warmup)}
 
 
 def kernels_only(sizes, device, reps):
@@ -198,13 +178,11 @@ def main():
     ap.add_argument('--kernels-only', action='store_true')
     ap.add_argument('--skip-whole-iteration', action='store_true')
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_deferred: needs the GPU (no CPU timing is meaningful)')
-    device = torch.device('cuda:0')
+    device = require_gpu('bench_deferred')
     if a.kernels_only:
         kernels_only(a.sizes, device, 20)
         return
-    lines = []
+    results = []
     for size in a.sizes:
         res = {'size': size, 'aa_samples': AA, 'alpha': True, 'lights': 4, 'iters': a.iters,
                'algorithmic_bytes': algorithmic_bytes(size, 4)}
@@ -224,12 +202,9 @@ def main():
         b = res['algorithmic_bytes']
         fa = res['a_shade_forward']['fused']['median_ms'] * 1e-3
         res['forward_call_rate_share_of_8TBps'] = b['forward'] / fa / PEAK_BYTES_PER_S
-        lines.append(json.dumps(res))
-        print(lines[-1], flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+        results.append(res)
+        print(json.dumps(res), flush=True)
+    emit(results, a.out, echo=False)
 
 
 if __name__ == '__main__':

@@ -17,7 +17,6 @@ the run fails if the profiler reports none.
 with a fixed pose, so that the share of the pose in an iteration is on record.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -26,9 +25,10 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools')]
 
 from redner_amd import pose_vertices        # noqa: E402
+from op_bench import count_launches, emit, require_gpu, time_alternating          # noqa: E402
 
 
 def torch_rotate_matrix(angles):
@@ -48,41 +48,6 @@ def torch_pose(sets, angles, translation):
     rotation = torch_rotate_matrix(angles)
     center = torch.mean(torch.cat(sets), 0)
     return [(v - center) @ torch.t(rotation) + center + translation for v in sets]
-
-
-def count_launches(step):
-    """Device kernels and copies of one step, by torch.profiler; a count the profiler cannot give is an error: the launch count
-    is one of the two claims this benchmark checks"""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        step()
-        torch.cuda.synchronize()
-    n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA'))
-    if n == 0:
-        raise RuntimeError('bench_pose: torch.profiler reported no device activity for a step')
-    return n
-
-
-def time_alternating(steps, iters, warmup):
-    for _ in range(warmup):
-        for f in steps.values():
-            f()
-    torch.cuda.synchronize()
-    times = {name: [] for name in steps}
-    for _ in range(iters):
-        for name, f in steps.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1))
-    out = {}
-    for name, ts in times.items():
-        ts = sorted(ts)
-        out[name] = {'median_ms': ts[len(ts) // 2], 'p10_ms': ts[len(ts) // 10], 'p90_ms': ts[(len(ts) * 9) // 10]}
-    return out
 
 
 def make_steps(spec, device):
@@ -118,7 +83,7 @@ def run_case(spec, device, iters, warmup):
     res['d_angles_rel_difference'] = rel(params['native'][0].grad, params['torch'][0].grad)
     res['d_translation_rel_difference'] = rel(params['native'][1].grad, params['torch'][1].grad)
     res['step'] = time_alternating(steps, iters, warmup)
-    res['launches'] = {name: count_launches(f) for name, f in steps.items()}
+    res['launches'] = {name: count_launches(f, 'bench_pose', required=True) for name, f in steps.items()}
     r = res['step']
     res['ratio'] = r['torch']['median_ms'] / r['native']['median_ms']
     print('%-12s step  torch %8.3f ms [%7.3f, %7.3f] %s launches   native %7.3f ms [%6.3f, %6.3f] %s launches   x%.1f   '
@@ -178,9 +143,7 @@ def main():
     ap.add_argument('--iteration', action='store_true', help='also one bunny_box iteration with each pose')
     ap.add_argument('--kernels-only', action='store_true', help='only the native steps, untimed: for a kernel trace')
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_pose: needs the GPU (no CPU timing is meaningful)')
-    device = torch.device('cuda:0')
+    device = require_gpu('bench_pose')
     if a.kernels_only:
         for spec in a.cases:
             step_native = make_steps(spec, device)[4]
@@ -191,13 +154,7 @@ def main():
     results = [run_case(spec, device, a.iters, a.warmup) for spec in a.cases]
     if a.iteration:
         results.append(run_iteration(device))
-    lines = [json.dumps(r) for r in results]
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
-    for line in lines:
-        print(line, flush=True)
+    emit(results, a.out)
 
 
 if __name__ == '__main__':

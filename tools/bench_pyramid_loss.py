@@ -18,7 +18,6 @@ the baseline, that is recorded and the native figures stand alone.
 loss in an iteration is on record.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -27,9 +26,10 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools')]
 
 from redner_amd import gaussian_pyramid_loss        # noqa: E402
+from op_bench import count_launches, emit, require_gpu, time_alternating          # noqa: E402
 
 COPY_BYTES_PER_S = 6.29e12
 
@@ -66,41 +66,6 @@ def traffic_bytes(h, w, c, num_levels):
     # forward: image + target read, levels 1.. written and (all but the last) read again; backward: image + target read, levels
     # 1.. read, their gradients written and read, d_image written
     return 4 * (2 * sizes[0] + sum(sizes[1:]) + sum(sizes[1:-1]) + 2 * sizes[0] + 3 * sum(sizes[1:]) + sizes[0])
-
-
-def count_launches(step):
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            step()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA'))
-        return n or None
-    except Exception as e:                          # the figure is optional; the timings are not
-        print('bench_pyramid_loss: launches not counted (%s)' % e, flush=True)
-        return None
-
-
-def time_alternating(steps, iters, warmup):
-    for _ in range(warmup):
-        for f in steps.values():
-            f()
-    torch.cuda.synchronize()
-    times = {name: [] for name in steps}
-    for _ in range(iters):
-        for name, f in steps.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1))
-    out = {}
-    for name, ts in times.items():
-        ts = sorted(ts)
-        out[name] = {'median_ms': ts[len(ts) // 2], 'p10_ms': ts[len(ts) // 10], 'p90_ms': ts[(len(ts) * 9) // 10]}
-    return out
 
 
 def make_steps(spec, device):
@@ -144,7 +109,7 @@ def run_case(spec, device, iters, warmup):
         res['loss_rel_difference'] = abs(last['torch'].item() - last['native'].item()) / abs(last['torch'].item())
         res['grad_rel_difference'] = float((images['torch'].grad - images['native'].grad).norm() / images['torch'].grad.norm())
     res['step'] = time_alternating(steps, iters, warmup)
-    res['launches'] = {name: count_launches(f) for name, f in steps.items()}
+    res['launches'] = {name: count_launches(f, 'bench_pyramid_loss') for name, f in steps.items()}
     bound_ms = traffic_bytes(h, w, c, num_levels) / COPY_BYTES_PER_S * 1e3
     res['native_traffic_bytes'], res['native_traffic_bound_ms'] = traffic_bytes(h, w, c, num_levels), bound_ms
     r = res['step']
@@ -205,9 +170,7 @@ def main():
     ap.add_argument('--iteration', action='store_true', help='also one bunny_box iteration with each loss')
     ap.add_argument('--kernels-only', action='store_true', help='only the native steps, untimed: for a kernel trace')
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_pyramid_loss: needs the GPU (no CPU timing is meaningful)')
-    device = torch.device('cuda:0')
+    device = require_gpu('bench_pyramid_loss')
     if a.kernels_only:
         for spec in a.cases:
             step_native = make_steps(spec, device)[4]
@@ -218,13 +181,7 @@ def main():
     results = [run_case(spec, device, a.iters, a.warmup) for spec in a.cases]
     if a.iteration:
         results.append(run_iteration(device))
-    lines = [json.dumps(r) for r in results]
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
-    for line in lines:
-        print(line, flush=True)
+    emit(results, a.out)
 
 
 if __name__ == '__main__':

@@ -16,7 +16,6 @@ times: launches, allocations, autograd and the Python around them included.  Lau
 (device kernels and copies of one step; `null` where the profiler reports none).
 """
 import argparse
-import json
 import math
 import os
 import sys
@@ -25,10 +24,11 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tools')]
 
 import redner_amd                                   # noqa: E402
 from redner_amd import render_pytorch               # noqa: E402
+from op_bench import count_launches, emit, require_gpu, time_alternating          # noqa: E402
 
 
 def _legendre(l, m, x):
@@ -93,42 +93,6 @@ def make_steps(res, bands, device):
     return coeffs, step_torch, step_native
 
 
-def count_launches(step):
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            step()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA'))
-        return n or None
-    except Exception as e:                          # the figure is optional; the timings are not
-        print('bench_sh_envmap: launches not counted (%s)' % e, flush=True)
-        return None
-
-
-def time_alternating(base, native, iters, warmup):
-    for _ in range(warmup):
-        base()
-        native()
-    torch.cuda.synchronize()
-    times = {'torch': [], 'native': []}
-    for _ in range(iters):
-        for name, f in (('torch', base), ('native', native)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1))
-    out = {}
-    for name, ts in times.items():
-        ts = sorted(ts)
-        out[name] = {'median_ms': ts[len(ts) // 2], 'p10_ms': ts[len(ts) // 10], 'p90_ms': ts[(len(ts) * 9) // 10]}
-    out['ratio'] = out['torch']['median_ms'] / out['native']['median_ms']
-    return out
-
-
 def run_case(spec, device, iters, warmup):
     h, w, bands = (int(s) for s in spec.split('x'))
     coeffs, step_torch, step_native = make_steps((h, w), bands, device)
@@ -138,9 +102,10 @@ def run_case(spec, device, iters, warmup):
            'image_max_abs_difference': float((a.values.mipmap[0] - b.values.mipmap[0]).abs().max()),
            'grad_rel_difference': float((coeffs['torch'].grad - coeffs['native'].grad).norm() / coeffs['torch'].grad.norm()),
            'tables_equal': bool(torch.equal(a.sample_cdf_xs, b.sample_cdf_xs) and torch.equal(a.sample_cdf_ys, b.sample_cdf_ys)),
-           'step': time_alternating(step_torch, step_native, iters, warmup),
-           'launches': {'torch': count_launches(step_torch), 'native': count_launches(step_native)}}
+           'step': time_alternating({'torch': step_torch, 'native': step_native}, iters, warmup),
+           'launches': {'torch': count_launches(step_torch, 'bench_sh_envmap'), 'native': count_launches(step_native, 'bench_sh_envmap')}}
     r = res['step']
+    r['ratio'] = r['torch']['median_ms'] / r['native']['median_ms']
     print('%-14s step  torch %8.3f ms [%7.3f, %7.3f] %s launches   native %7.3f ms [%6.3f, %6.3f] %s launches   x%.1f'
           % (spec, r['torch']['median_ms'], r['torch']['p10_ms'], r['torch']['p90_ms'], res['launches']['torch'],
              r['native']['median_ms'], r['native']['p10_ms'], r['native']['p90_ms'], res['launches']['native'], r['ratio']), flush=True)
@@ -155,9 +120,7 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--kernels-only', action='store_true', help='only the native steps, untimed: for a kernel trace')
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_sh_envmap: needs the GPU (no CPU timing is meaningful)')
-    device = torch.device('cuda:0')
+    device = require_gpu('bench_sh_envmap')
     if a.kernels_only:
         for spec in a.cases:
             h, w, bands = (int(s) for s in spec.split('x'))
@@ -166,13 +129,7 @@ def main():
                 step_native()
             torch.cuda.synchronize()
         return
-    lines = [json.dumps(run_case(spec, device, a.iters, a.warmup)) for spec in a.cases]
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
-    for line in lines:
-        print(line, flush=True)
+    emit([run_case(spec, device, a.iters, a.warmup) for spec in a.cases], a.out)
 
 
 if __name__ == '__main__':

@@ -14,7 +14,6 @@ mask) and the native side a MeshTopology built once.  These are CALL times: laun
 the Python around them included -- at the small sizes they measure those overheads, not the kernels.
 """
 import argparse
-import json
 import math
 import os
 import sys
@@ -26,7 +25,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools')]
 
 from golden import make_mesh_golden as mg          # noqa: E402
 from redner_amd import shape                       # noqa: E402
-from bench_vertex_normals import time_alternating  # noqa: E402
+from bench_vertex_normals import against_torch     # noqa: E402   (torch against native, with their speedup)
+from op_bench import emit, require_gpu             # noqa: E402
 
 SCHEMES = ('reciprocal', 'uniform', 'cotangent')
 LMD = 0.1
@@ -104,9 +104,9 @@ def mesh_cases(name, vertices, indices, device, iters, warmup):
             shape.mesh_laplacian(x, idx32, scheme, control, topology=topology).backward(up)
 
         res[scheme] = {'max_abs_difference_of_shift': diff,
-                       'a_one_step': time_alternating(step_torch, step_native, iters, warmup),
-                       'b_ten_steps': time_alternating(lambda: step_torch(10), lambda: step_native(10), max(iters // 2, 5), warmup),
-                       'c_laplacian_forward_backward': time_alternating(both_torch, both_native, iters, warmup)}
+                       'a_one_step': against_torch(step_torch, step_native, iters, warmup),
+                       'b_ten_steps': against_torch(lambda: step_torch(10), lambda: step_native(10), max(iters // 2, 5), warmup),
+                       'c_laplacian_forward_backward': against_torch(both_torch, both_native, iters, warmup)}
         for key in ('a_one_step', 'b_ten_steps', 'c_laplacian_forward_backward'):
             r = res[scheme][key]
             print('%-16s V %8d T %8d %-10s %-28s torch %8.3f ms [%7.3f, %7.3f]   native %7.3f ms [%6.3f, %6.3f]   x%.1f'
@@ -122,22 +122,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_smooth: needs the GPU (no CPU timing is meaningful)')
-    device = torch.device('cuda:0')
-    lines = []
+    device = require_gpu('bench_smooth')
+    results = []
     for spec in a.spheres:
         rows, cols = (int(s) for s in spec.split('x'))
         v, f = mg.uv_sphere(rows, cols, 22)
-        lines.append(json.dumps(mesh_cases('sphere' + spec, torch.from_numpy(v), torch.from_numpy(f), device, a.iters, a.warmup)))
+        results.append(mesh_cases('sphere' + spec, torch.from_numpy(v), torch.from_numpy(f), device, a.iters, a.warmup))
     v, f = mg.mesh('fan300')
-    lines.append(json.dumps(mesh_cases('fan300', v, f, device, a.iters, a.warmup)))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
-    for line in lines:
-        print(line, flush=True)
+    results.append(mesh_cases('fan300', v, f, device, a.iters, a.warmup))
+    emit(results, a.out)
 
 
 if __name__ == '__main__':

@@ -25,9 +25,10 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools')]
 
 from redner_amd import texture as tx          # noqa: E402
+import op_bench                                # noqa: E402
 
 PEAK_BYTES_PER_S = 8.0e12
 
@@ -48,24 +49,8 @@ def torch_mipmap(texels):
     return mipmap
 
 
-def time_alternating(base, native, iters, warmup):
-    for _ in range(warmup):
-        base()
-        native()
-    torch.cuda.synchronize()
-    times = {'torch': [], 'native': []}
-    for _ in range(iters):
-        for name, f in (('torch', base), ('native', native)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1))
-    out = {}
-    for name, ts in times.items():
-        ts = sorted(ts)
-        out[name] = {'median_ms': ts[len(ts) // 2], 'p10_ms': ts[len(ts) // 10], 'p90_ms': ts[(len(ts) * 9) // 10]}
+def against_torch(base, native, iters, warmup):
+    out = op_bench.time_alternating({'torch': base, 'native': native}, iters, warmup)
     t, f = out['torch'], out['native']
     spread = max(t['p90_ms'] - t['p10_ms'], f['p90_ms'] - f['p10_ms'])
     out['speedup'] = t['median_ms'] / f['median_ms']
@@ -109,8 +94,8 @@ def pyramid_cases(size, device, iters, warmup):
         return run
 
     return {'max_abs_difference_of_levels': err,
-            'a_forward': time_alternating(fwd(torch_mipmap), fwd(tx.generate_mipmap), iters, warmup),
-            'b_forward_backward': time_alternating(both(torch_mipmap), both(tx.generate_mipmap), iters, warmup)}
+            'a_forward': against_torch(fwd(torch_mipmap), fwd(tx.generate_mipmap), iters, warmup),
+            'b_forward_backward': against_torch(both(torch_mipmap), both(tx.generate_mipmap), iters, warmup)}
 
 
 def fit_case(device, iters, warmup):
@@ -146,8 +131,8 @@ def fit_case(device, iters, warmup):
                 torch.autograd.backward(build(t), u)
         return run
 
-    whole = time_alternating(iteration(torch_mipmap), iteration(tx.generate_mipmap), iters, warmup)
-    alone = time_alternating(pyramids(torch_mipmap), pyramids(tx.generate_mipmap), iters, warmup)
+    whole = against_torch(iteration(torch_mipmap), iteration(tx.generate_mipmap), iters, warmup)
+    alone = against_torch(pyramids(torch_mipmap), pyramids(tx.generate_mipmap), iters, warmup)
     share = {k: alone[k]['median_ms'] / whole[k]['median_ms'] for k in ('torch', 'native')}
     return {'c_fit_iteration': whole, 'c_three_pyramids_forward_backward': alone, 'c_pyramid_share_of_iteration': share}
 
@@ -172,30 +157,25 @@ def main():
     ap.add_argument('--kernels-only', action='store_true')
     ap.add_argument('--skip-fit', action='store_true')
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_texture: needs the GPU (no CPU timing is meaningful)')
-    device = torch.device('cuda:0')
+    device = op_bench.require_gpu('bench_texture')
     if a.kernels_only:
         kernels_only(a.sizes, device, 20)
         return
-    lines = []
+    results = []
     for size in a.sizes:
         res = {'size': size, 'channels': 3, 'iters': a.iters, 'algorithmic_bytes': algorithmic_bytes(size)}
         res.update(pyramid_cases(size, device, a.iters, a.warmup))
         for key in ('a_forward', 'b_forward_backward'):
             report('%d^2 x 3' % size, key, res[key])
-        lines.append(json.dumps(res))
-        print(lines[-1], flush=True)
+        results.append(res)
+        print(json.dumps(res), flush=True)
     if not a.skip_fit:
         res = fit_case(device, a.iters, a.warmup)
         for key in ('c_fit_iteration', 'c_three_pyramids_forward_backward'):
             report('fit', key, res[key])
-        lines.append(json.dumps(res))
-        print(lines[-1], flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+        results.append(res)
+        print(json.dumps(res), flush=True)
+    op_bench.emit(results, a.out, echo=False)
 
 
 if __name__ == '__main__':

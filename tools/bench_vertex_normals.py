@@ -13,17 +13,17 @@ events; the median and the 10th / 90th percentiles are reported.  These are CALL
 allocation of outputs and scratch and the Python around them -- at the small sizes they measure those overheads, not the kernels.
 """
 import argparse
-import json
 import os
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools')]
 
 from golden import make_mesh_golden as mg          # noqa: E402
 from redner_amd import shape                       # noqa: E402
+import op_bench                                    # noqa: E402
 
 
 def _safe_sqrt(sq):
@@ -78,24 +78,8 @@ def torch_vertex_normals(v, idx, scheme):
     return torch.where(kept[:, None], s / torch.where(kept, length, torch.ones_like(length))[:, None], n_max)
 
 
-def time_alternating(base, native, iters, warmup):
-    for _ in range(warmup):
-        base()
-        native()
-    torch.cuda.synchronize()
-    times = {'torch': [], 'native': []}
-    for _ in range(iters):
-        for name, f in (('torch', base), ('native', native)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            f()
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1))
-    out = {}
-    for name, ts in times.items():
-        ts = sorted(ts)
-        out[name] = {'median_ms': ts[len(ts) // 2], 'p10_ms': ts[len(ts) // 10], 'p90_ms': ts[(len(ts) * 9) // 10]}
+def against_torch(base, native, iters, warmup):
+    out = op_bench.time_alternating({'torch': base, 'native': native}, iters, warmup)
     out['speedup'] = out['torch']['median_ms'] / out['native']['median_ms']
     return out
 
@@ -109,8 +93,7 @@ def time_plan(indices, num_vertices, iters):
         e1.record()
         e1.synchronize()
         ts.append(e0.elapsed_time(e1))
-    ts = sorted(ts[2:])
-    return {'median_ms': ts[len(ts) // 2], 'p10_ms': ts[len(ts) // 10], 'p90_ms': ts[(len(ts) * 9) // 10]}
+    return op_bench.summary(ts[2:])
 
 
 def mesh_cases(name, vertices, indices, schemes, device, iters, warmup):
@@ -143,8 +126,8 @@ def mesh_cases(name, vertices, indices, schemes, device, iters, warmup):
             shape.compute_vertex_normal(x, idx32, scheme, topology=topology).backward(up)
 
         res[scheme] = {'max_abs_difference_of_normals': diff,
-                       'a_forward': time_alternating(fwd_torch, fwd_native, iters, warmup),
-                       'b_forward_backward': time_alternating(both_torch, both_native, iters, warmup)}
+                       'a_forward': against_torch(fwd_torch, fwd_native, iters, warmup),
+                       'b_forward_backward': against_torch(both_torch, both_native, iters, warmup)}
         for key in ('a_forward', 'b_forward_backward'):
             r = res[scheme][key]
             print('%-16s V %8d T %8d %-9s %-18s torch %8.3f ms [%7.3f, %7.3f]   native %7.3f ms [%6.3f, %6.3f]   x%.1f'
@@ -163,24 +146,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_vertex_normals: needs the GPU (no CPU timing is meaningful)')
-    device = torch.device('cuda:0')
-    lines = []
+    device = op_bench.require_gpu('bench_vertex_normals')
+    results = []
     for spec in a.spheres:
         rows, cols = (int(s) for s in spec.split('x'))
         v, f = mg.uv_sphere(rows, cols, 22)
         # (cotangent on a sphere this fine falls back to 'max' everywhere: both sums are computed, which is what is timed)
         res = mesh_cases('sphere' + spec, torch.from_numpy(v), torch.from_numpy(f), ('max', 'cotangent'), device, a.iters, a.warmup)
-        lines.append(json.dumps(res))
+        results.append(res)
     v, f = mg.mesh('fan300')
-    lines.append(json.dumps(mesh_cases('fan300', v, f, ('max',), device, a.iters, a.warmup)))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
-    for line in lines:
-        print(line, flush=True)
+    results.append(mesh_cases('fan300', v, f, ('max',), device, a.iters, a.warmup))
+    op_bench.emit(results, a.out)
 
 
 if __name__ == '__main__':
