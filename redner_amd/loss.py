@@ -51,13 +51,15 @@ class GaussianPyramidLoss(torch.autograd.Function):
         a, b = image.detach().contiguous(), target.detach().contiguous()
         loss, terms, saved = _forward(rd, a, b, num_levels, clamp, weights)
         ctx.rd, ctx.options = rd, (num_levels, clamp, weights)
-        ctx.image, ctx.target, ctx.scratch = a, b, saved
+        # (for a contiguous input a / b is the caller's own memory: saved this way, an in-place edit before backward raises)
+        ctx.save_for_backward(a, b, saved)
         ctx.mark_non_differentiable(terms)
         return loss, terms
 
     @staticmethod
     def backward(ctx, d_loss, _d_terms):
-        rd, a, b = ctx.rd, ctx.image, ctx.target
+        rd = ctx.rd
+        a, b, saved = ctx.saved_tensors
         num_levels, clamp, weights = ctx.options
         batch, height, width, channels = _geometry(a)
         use_gpu, index = place(a)
@@ -66,7 +68,7 @@ class GaussianPyramidLoss(torch.autograd.Function):
         d_target = torch.empty_like(b) if ctx.needs_input_grad[1] else None
         _, bwd = rd.pyramid_loss_scratch(batch, height, width, channels, num_levels)
         work = scratch(bwd, a.device)
-        rd.pyramid_loss_backward(ptr(rd, a), ptr(rd, b), ptr(rd, ctx.scratch), 2 * ctx.scratch.numel(), ptr(rd, g), ptr(rd, d_image),
+        rd.pyramid_loss_backward(ptr(rd, a), ptr(rd, b), ptr(rd, saved), 2 * saved.numel(), ptr(rd, g), ptr(rd, d_image),
                                  ptr(rd, d_target), ptr(rd, work), bwd, batch, height, width, channels, num_levels, weights,
                                  clamp or 0.0, use_gpu, index)
         return (d_image if ctx.needs_input_grad[0] else None), d_target, None, None, None, None
@@ -103,8 +105,8 @@ def _checked(image, target, num_levels, clamp, weights):
 def gaussian_pyramid_loss(image, target, num_levels=5, clamp=None, weights=None, return_terms=False, backend=None):
     """The loss of the module's docstring as a 0-dim fp32 tensor on the inputs' device; differentiable with respect to `image`
     and `target`.  clamp: clamp image - target to [-clamp, clamp] first (tutorial 05's clamp(-1, 1)); weights: one factor per
-    level (a coarse-to-fine schedule).  With return_terms=True also the detached fp64 [num_levels] per-level terms, summed over
-    the batch."""
+    level (a coarse-to-fine schedule), rounded to fp32.  With return_terms=True also the detached fp64 [num_levels] per-level
+    terms, summed over the batch."""
     num_levels, clamp, weights = _checked(image, target, num_levels, clamp, weights)
     with named('gaussian_pyramid_loss'):
         loss, terms = GaussianPyramidLoss.apply(image, target, num_levels, clamp, weights, backend)

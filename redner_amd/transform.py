@@ -35,12 +35,14 @@ class RotateMatrix(torch.autograd.Function):
         a = angles.detach().contiguous()
         matrix = torch.empty(3, 3, dtype=torch.float32, device=a.device)
         rd.rotate_matrix(ptr(rd, a), ptr(rd, matrix), *place(a))
-        ctx.rd, ctx.angles = rd, a
+        ctx.rd = rd
+        ctx.save_for_backward(a)
         return matrix
 
     @staticmethod
     def backward(ctx, d_matrix):
-        rd, a = ctx.rd, ctx.angles
+        rd = ctx.rd
+        a, = ctx.saved_tensors
         g = upstream(d_matrix, a.device)
         d_angles = torch.empty(3, dtype=torch.float32, device=a.device)
         rd.rotate_matrix_backward(ptr(rd, a), ptr(rd, g), ptr(rd, d_angles), *place(a))
@@ -73,14 +75,20 @@ class PoseVertices(torch.autograd.Function):
         rd = backend or _default_backend
         sets = [v.detach().contiguous() for v in vertices]
         a = angles.detach().contiguous()
-        out, saved = _forward(rd, sets, a, translation.detach().contiguous(), None if center is None else center.detach().contiguous())
-        ctx.rd, ctx.sets, ctx.counts, ctx.angles, ctx.saved, ctx.own = rd, sets, [int(v.shape[0]) for v in sets], a, saved, center is None
+        c = None if center is None else center.detach().contiguous()
+        out, saved = _forward(rd, sets, a, translation.detach().contiguous(), c)
+        ctx.rd, ctx.counts, ctx.saved, ctx.own = rd, [int(v.shape[0]) for v in sets], saved, c is None
+        # what the backward call reads, and a given centre (its copy in `saved` is what is read): for a contiguous input that is
+        # the caller's own memory, and saved this way an in-place edit before backward raises.  ctx.saved stays for readers.
+        ctx.save_for_backward(a, saved, *sets, *(() if c is None else (c,)))
         ctx.set_materialize_grads(False)
         return tuple(out)
 
     @staticmethod
     def backward(ctx, *d_out):
-        rd, sets, counts, a = ctx.rd, ctx.sets, ctx.counts, ctx.angles
+        rd, counts = ctx.rd, ctx.counts
+        a, saved = ctx.saved_tensors[:2]
+        sets = list(ctx.saved_tensors[2:2 + len(counts)])
         device = sets[0].device
         g = [upstream(d, device) for d in d_out]
         d_vertices = [torch.empty_like(v) if ctx.needs_input_grad[4 + k] else None for k, v in enumerate(sets)]
@@ -88,7 +96,7 @@ class PoseVertices(torch.autograd.Function):
         d_center = None if ctx.own else torch.empty(3, dtype=torch.float32, device=device)
         _, floats = rd.pose_scratch(counts)
         work = scratch(floats, device)
-        rd.pose_vertices_backward([ptr(rd, v) for v in sets], counts, ptr(rd, a), ptr(rd, ctx.saved), ctx.own, [ptr(rd, d) for d in g],
+        rd.pose_vertices_backward([ptr(rd, v) for v in sets], counts, ptr(rd, a), ptr(rd, saved), ctx.own, [ptr(rd, d) for d in g],
                                   [ptr(rd, d) for d in d_vertices] if any(d is not None for d in d_vertices) else None,
                                   ptr(rd, d_angles), ptr(rd, d_translation), ptr(rd, d_center), ptr(rd, work), floats, *place(device))
         return (d_angles, d_translation, d_center, None) + tuple(d_vertices)

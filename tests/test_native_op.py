@@ -27,6 +27,12 @@ def test_upstream():
     assert torch.equal(out.double(), g)
     ready = torch.ones(4, 3)
     assert _op.upstream(ready, CPU).data_ptr() == ready.data_ptr()
+    # what out.sum().backward() hands over: one element expanded with strides of 0
+    expanded = torch.full((), 3.0).expand(4, 3)
+    assert expanded.stride() == (0, 0) and not expanded.is_contiguous()
+    out = _op.upstream(expanded, CPU)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (4, 3) and out.stride() == (3, 1)
+    assert out.untyped_storage().nbytes() >= 4 * 12 and bool((out == 3.0).all())
 
 
 def test_named():

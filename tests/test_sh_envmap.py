@@ -197,41 +197,45 @@ def _definition(res, bands):
     return torch.stack(amp), torch.stack(damp), orders, theta, phi
 
 
+def _reference64_of(res, coeffs, upstream):
+    """The fp64 image and d_coeffs of coeffs [C, N] at `res` under the upstream gradient [H, W, C], and the two bars."""
+    n, c = int(coeffs.shape[1]), int(coeffs.shape[0])
+    bands = int(math.sqrt(n))
+    nb = bands * bands
+    amp, damp, orders, theta, phi = _definition(res, bands)
+    trig = torch.stack([torch.ones_like(phi) if m == 0 else (torch.cos(m * phi) if m > 0 else torch.sin(-m * phi)) for m in orders])
+    basis = amp[:, :, None] * trig[:, None, :]                                    # [nb, H, W]
+    coeffs = coeffs.double()[:, :nb]                                               # [C, nb]
+    unclamped = torch.einsum('ihw,ci->hwc', basis, coeffs)
+    image = unclamped.clamp(min=0.0)
+    weight = torch.where(unclamped > 0, 1.0, torch.where(unclamped == 0, 0.5, 0.0)).double()
+    gw = upstream.double() * weight
+    d_coeffs = torch.zeros(c, n, dtype=torch.float64)
+    d_coeffs[:, :nb] = torch.einsum('ihw,hwc->ci', basis, gw)
+    # the error of one basis function at one pixel, in units of u (without the running sum)
+    m_abs = torch.tensor([abs(m) for m in orders], dtype=torch.float64)
+    per_basis = (3.0 * m_abs[:, None, None] * phi[None, None, :] + 4.0 * bands + 4.0) * amp.abs()[:, :, None] + \
+        ((2.0 * theta * torch.sin(theta) + 0.5)[None, :] * damp.abs())[:, :, None]  # [nb, H, W]
+    s_a = torch.einsum('ih,ci->hc', amp.abs(), coeffs.abs())[:, None, :]
+    forward_bar = U * (torch.einsum('ihw,ci->hwc', per_basis, coeffs.abs()) + nb * s_a)
+    gradient_bar = torch.zeros(c, n, dtype=torch.float64)
+    gradient_bar[:, :nb] = U * torch.einsum('ihw,hwc->ci', per_basis, gw.abs())
+    s = torch.einsum('ihw,ci->hwc', basis.abs(), coeffs.abs())
+    return image.numpy(), d_coeffs.numpy(), forward_bar.numpy(), gradient_bar.numpy(), s.numpy()
+
+
 def _reference64(name):
     """Computed once per case and shared by the harness leg and the GPU legs: the fp64 image and d_coeffs, and the two bars."""
     if name not in _cache:
         res, n, c = ms.case_shape(name)
-        bands = int(math.sqrt(n))
-        nb = bands * bands
-        amp, damp, orders, theta, phi = _definition(res, bands)
-        trig = torch.stack([torch.ones_like(phi) if m == 0 else (torch.cos(m * phi) if m > 0 else torch.sin(-m * phi)) for m in orders])
-        basis = amp[:, :, None] * trig[:, None, :]                                    # [nb, H, W]
-        coeffs = ms.sh_coeffs(name).double()[:, :nb]                                   # [C, nb]
-        unclamped = torch.einsum('ihw,ci->hwc', basis, coeffs)
-        image = unclamped.clamp(min=0.0)
-        weight = torch.where(unclamped > 0, 1.0, torch.where(unclamped == 0, 0.5, 0.0)).double()
-        gw = ms.sh_upstream(name).double() * weight
-        d_coeffs = torch.zeros(c, n, dtype=torch.float64)
-        d_coeffs[:, :nb] = torch.einsum('ihw,hwc->ci', basis, gw)
-        # the error of one basis function at one pixel, in units of u (without the running sum)
-        m_abs = torch.tensor([abs(m) for m in orders], dtype=torch.float64)
-        per_basis = (3.0 * m_abs[:, None, None] * phi[None, None, :] + 4.0 * bands + 4.0) * amp.abs()[:, :, None] + \
-            ((2.0 * theta * torch.sin(theta) + 0.5)[None, :] * damp.abs())[:, :, None]  # [nb, H, W]
-        s_a = torch.einsum('ih,ci->hc', amp.abs(), coeffs.abs())[:, None, :]
-        forward_bar = U * (torch.einsum('ihw,ci->hwc', per_basis, coeffs.abs()) + nb * s_a)
-        gradient_bar = torch.zeros(c, n, dtype=torch.float64)
-        gradient_bar[:, :nb] = U * torch.einsum('ihw,hwc->ci', per_basis, gw.abs())
-        s = torch.einsum('ihw,ci->hwc', basis.abs(), coeffs.abs())
-        _cache[name] = (image.numpy(), d_coeffs.numpy(), forward_bar.numpy(), gradient_bar.numpy(), s.numpy())
+        assert tuple(ms.sh_coeffs(name).shape) == (c, n)
+        _cache[name] = _reference64_of(res, ms.sh_coeffs(name), ms.sh_upstream(name))
     return _cache[name]
 
 
-DEFINITION_CASES = ['1x7_o2', '5x3_o3', '16x32_o4', '33x17_o6', '64x129_o8', '33x17_o3_c5', '16x32_n17']
-
-
-def _run_definition(backend, device, name, tag):
-    want_image, want_grad, forward_bar, gradient_bar, s = _reference64(name)
-    image, d_coeffs = _native(backend, device, name)
+def _hold_definition(image, d_coeffs, reference, name, tag):
+    """image and d_coeffs (numpy) within the per-element bars of `reference` (_reference64_of)"""
+    want_image, want_grad, forward_bar, gradient_bar, s = reference
     err, gerr = np.abs(image.astype(np.float64) - want_image), np.abs(d_coeffs.astype(np.float64) - want_grad)
     worst = float((err / forward_bar).max())
     gworst = float(np.max(np.where(gradient_bar > 0, gerr / np.where(gradient_bar > 0, gradient_bar, 1.0), np.where(gerr > 0, np.inf, 0.0))))
@@ -243,6 +247,14 @@ def _run_definition(backend, device, name, tag):
         'd_coeffs': {'rel_l2': gworst, 'tol': 1.0, 'flipped_rows': 0, 'measure': 'max over the entries of |error| / GRADIENT_BAR'}}, tag)
     assert worst <= 1.0, (name, worst)
     assert gworst <= 1.0, (name, gworst)
+
+
+DEFINITION_CASES = ['1x7_o2', '5x3_o3', '16x32_o4', '33x17_o6', '64x129_o8', '33x17_o3_c5', '16x32_n17']
+
+
+def _run_definition(backend, device, name, tag):
+    image, d_coeffs = _native(backend, device, name)
+    _hold_definition(image, d_coeffs, _reference64(name), name, tag)
 
 
 @pytest.mark.parametrize('name', DEFINITION_CASES)
