@@ -253,6 +253,13 @@ def load(path=None):
     return lib
 
 
+def use(handle, path):
+    """Make a library that load() returned earlier the current one again (tools that alternate two builds in one process).
+    Nothing in the package keeps a handle across calls: every entry point asks lib(); a Scene or MeshTopology keeps the one it was built with."""
+    global _lib, _lib_path
+    _lib, _lib_path = handle, path
+
+
 def lib():
     if _lib is None:
         load()

@@ -33,12 +33,13 @@ RDR_FN double bilerp_eval(const float *texels, int ch, int c, const Bilerp &b) {
            f10 * b.u * (1.f - b.v) + f11 * b.u * b.v;
 }
 
-RDR_FN void trilinear(const TexD &tex, V2 uv, double level, double *out) {
+// f(c, value) for every channel c of the texture, in channel order: a texture of any width needs no per-lane array.
+template <class F> RDR_FN void trilinear_each(const TexD &tex, V2 uv, double level, const F &f) {
     int ch = tex.channels;
     if (level <= 0 || level >= tex.num_levels - 1) {
         int li = level <= 0 ? 0 : tex.num_levels - 1;
         Bilerp b = bilerp_setup(tex, li, uv);
-        for (int c = 0; c < ch; ++c) out[c] = bilerp_eval(tex.texels[li], ch, c, b);
+        for (int c = 0; c < ch; ++c) f(c, bilerp_eval(tex.texels[li], ch, c, b));
     } else {
         int li = (int)floor(level);
         double ld = level - li;
@@ -46,9 +47,12 @@ RDR_FN void trilinear(const TexD &tex, V2 uv, double level, double *out) {
         for (int c = 0; c < ch; ++c) {
             double a0 = bilerp_eval(tex.texels[li], ch, c, b0);
             double a1 = bilerp_eval(tex.texels[li + 1], ch, c, b1);
-            out[c] = a0 * (1 - ld) + a1 * ld;
+            f(c, a0 * (1 - ld) + a1 * ld);
         }
     }
+}
+RDR_FN void trilinear(const TexD &tex, V2 uv, double level, double *out) {
+    trilinear_each(tex, uv, level, [out](int c, double x) { out[c] = x; });
 }
 
 RDR_FN double tex_level(const TexD &tex, V2 du, V2 dv) {
@@ -56,15 +60,19 @@ RDR_FN double tex_level(const TexD &tex, V2 du, V2 dv) {
     return log(dmax(fp, double(1e-8f))) / log(2.0);   // src/redner.h:112-114
 }
 
-// out[channels] = texture value at the shading point.
-RDR_FN void tex_fetch(const TexD &tex, V2 uv_, V2 du_, V2 dv_, double *out) {
+// f(c, value at the shading point) for every channel c, in channel order.
+template <class F> RDR_FN void tex_fetch_each(const TexD &tex, V2 uv_, V2 du_, V2 dv_, const F &f) {
     if (tex.width[0] <= 0 && tex.height[0] <= 0) {
-        for (int c = 0; c < tex.channels; ++c) out[c] = tex.texels[0][c];
+        for (int c = 0; c < tex.channels; ++c) f(c, (double)tex.texels[0][c]);
         return;
     }
     V2 sc = v2(tex.uv_scale[0], tex.uv_scale[1]);
     V2 uv = uv_ * sc, du = du_ * sc.x, dv = dv_ * sc.y;
-    trilinear(tex, uv, tex_level(tex, du, dv), out);
+    trilinear_each(tex, uv, tex_level(tex, du, dv), f);
+}
+// out[channels] = texture value at the shading point (the 1- and 3-channel textures of the BSDF).
+RDR_FN void tex_fetch(const TexD &tex, V2 uv_, V2 du_, V2 dv_, double *out) {
+    tex_fetch_each(tex, uv_, du_, dv_, [out](int c, double x) { out[c] = x; });
 }
 
 RDR_FN void adj_bilerp(const TexD &tex, double *const *gtexels, int li, V2 uv, int ch, int c, double o_bar,
@@ -104,11 +112,20 @@ RDR_FN void adj_bilerp_rgb(const TexD &tex, double *const *gtexels, int li, V2 u
     }
 }
 
-RDR_FN void adj_tex_fetch(const TexD &tex, V2 uv_, V2 du_, V2 dv_, const double *o_bar, const GTex &g,
+// Upstream values of adj_tex_fetch: o_bar(c) for channel c, formed as they are asked for -- a texture of any width needs no
+// per-lane array.  ArrayBar: the one or three values of the BSDF's own textures, in memory.
+struct ArrayBar {
+    const double *p;
+    RDR_FN double operator()(int c) const { return p[c]; }
+    RDR_FN const double *triple(double *) const { return p; }      // the three values of an rgb texture
+};
+
+template <class OBar>
+RDR_FN void adj_tex_fetch(const TexD &tex, V2 uv_, V2 du_, V2 dv_, const OBar &o_bar, const GTex &g,
                           V2 &uv_bar_, V2 &du_bar_, V2 &dv_bar_) {
     int ch = tex.channels;
     if (tex.width[0] <= 0 && tex.height[0] <= 0) {
-        if (g.texels[0]) { if (ch == 3) accum_triple(g.texels[0], o_bar[0], o_bar[1], o_bar[2]); else for (int c = 0; c < ch; ++c) accum(g.texels[0] + c, o_bar[c]); }
+        if (g.texels[0]) { if (ch == 3) accum_triple(g.texels[0], o_bar(0), o_bar(1), o_bar(2)); else for (int c = 0; c < ch; ++c) accum(g.texels[0] + c, o_bar(c)); }
         return;
     }
     V2 sc = v2(tex.uv_scale[0], tex.uv_scale[1]);
@@ -122,8 +139,10 @@ RDR_FN void adj_tex_fetch(const TexD &tex, V2 uv_, V2 du_, V2 dv_, const double 
     if (level <= 0 || level >= tex.num_levels - 1) {
         int li = level <= 0 ? 0 : tex.num_levels - 1;
         double ub = 0, vb = 0;
-        if (ch == 3) adj_bilerp_rgb(tex, g.texels, li, uv, o_bar, ub, vb);
-        else for (int c = 0; c < ch; ++c) adj_bilerp(tex, g.texels, li, uv, ch, c, o_bar[c], ub, vb);
+        if (ch == 3) {
+            double o3[3];
+            adj_bilerp_rgb(tex, g.texels, li, uv, o_bar.triple(o3), ub, vb);
+        } else for (int c = 0; c < ch; ++c) adj_bilerp(tex, g.texels, li, uv, ch, c, o_bar(c), ub, vb);
         uv_bar.x += ub * tex.width[li]; uv_bar.y += vb * tex.height[li];
     } else {
         int li = (int)floor(level);
@@ -133,14 +152,14 @@ RDR_FN void adj_tex_fetch(const TexD &tex, V2 uv_, V2 du_, V2 dv_, const double 
         for (int c = 0; c < ch; ++c) {
             double a0 = bilerp_eval(tex.texels[li], ch, c, b0);
             double a1 = bilerp_eval(tex.texels[li + 1], ch, c, b1);
-            level_bar += o_bar[c] * (a1 - a0);
+            level_bar += o_bar(c) * (a1 - a0);
             if (ch == 3) continue;
-            adj_bilerp(tex, g.texels, li, uv, ch, c, o_bar[c] * (1 - ld), u0b, v0b);
-            adj_bilerp(tex, g.texels, li + 1, uv, ch, c, o_bar[c] * ld, u1b, v1b);
+            adj_bilerp(tex, g.texels, li, uv, ch, c, o_bar(c) * (1 - ld), u0b, v0b);
+            adj_bilerp(tex, g.texels, li + 1, uv, ch, c, o_bar(c) * ld, u1b, v1b);
         }
         if (ch == 3) {          // (the two levels have separate accumulators: per level the channels still arrive in order)
-            const double lo_bar[3] = {o_bar[0] * (1 - ld), o_bar[1] * (1 - ld), o_bar[2] * (1 - ld)};
-            const double hi_bar[3] = {o_bar[0] * ld, o_bar[1] * ld, o_bar[2] * ld};
+            const double lo_bar[3] = {o_bar(0) * (1 - ld), o_bar(1) * (1 - ld), o_bar(2) * (1 - ld)};
+            const double hi_bar[3] = {o_bar(0) * ld, o_bar(1) * ld, o_bar(2) * ld};
             adj_bilerp_rgb(tex, g.texels, li, uv, lo_bar, u0b, v0b);
             adj_bilerp_rgb(tex, g.texels, li + 1, uv, hi_bar, u1b, v1b);
         }
@@ -178,11 +197,11 @@ RDR_FN void adj_tex3(const TexD &tex, const Surf &sp, V3 o_bar, const GTex &g, S
         return;
     }
     double ob[3] = {o_bar.x, o_bar.y, o_bar.z};
-    adj_tex_fetch(tex, sp.uv, sp.du_dxy, sp.dv_dxy, ob, g, sp_bar.uv, sp_bar.du_dxy, sp_bar.dv_dxy);
+    adj_tex_fetch(tex, sp.uv, sp.du_dxy, sp.dv_dxy, ArrayBar{ob}, g, sp_bar.uv, sp_bar.du_dxy, sp_bar.dv_dxy);
 }
 RDR_FN void adj_tex1(const TexD &tex, const Surf &sp, double o_bar, const GTex &g, Surf &sp_bar) {
     if (sp.plain) { if (g.texels[0]) accum(g.texels[0], o_bar); return; }
-    adj_tex_fetch(tex, sp.uv, sp.du_dxy, sp.dv_dxy, &o_bar, g, sp_bar.uv, sp_bar.du_dxy, sp_bar.dv_dxy);
+    adj_tex_fetch(tex, sp.uv, sp.du_dxy, sp.dv_dxy, ArrayBar{&o_bar}, g, sp_bar.uv, sp_bar.du_dxy, sp_bar.dv_dxy);
 }
 
 // ---- normal mapping (src/material.h:274-351) ----------------------------------------------------

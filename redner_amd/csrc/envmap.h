@@ -54,7 +54,7 @@ RDR_FN void adj_envmap_eval(const EnvmapD &env, V3 dir, const RayDiff &rd, V3 o_
     GTex none;
     for (int i = 0; i < kMaxMip; ++i) none.texels[i] = nullptr;
     none.uv_scale = nullptr;
-    adj_tex_fetch(env.values, e.uv, e.du_dxy, e.dv_dxy, ob, g ? g->values : none, uv_bar, du_bar, dv_bar);
+    adj_tex_fetch(env.values, e.uv, e.du_dxy, e.dv_dxy, ArrayBar{ob}, g ? g->values : none, uv_bar, du_bar, dv_bar);
     double dvdy_bar = dv_bar.x * e.ld_dx.y + dv_bar.y * e.ld_dy.y;
     V3 lddx_bar = V3{0.0, dv_bar.x * e.dv_dy_l, 0.0};
     V3 lddy_bar = V3{0.0, dv_bar.y * e.dv_dy_l, 0.0};

@@ -69,7 +69,6 @@ ChannelLayout layout_of(const rdr_render_options &o, int max_generic) {
     ChannelLayout l;
     l.nd = 0; l.radiance_dim = -1;
     if (o.num_channels > kMaxChannels) throw std::runtime_error("render: too many channels");
-    if (max_generic > kMaxGeneric) throw std::runtime_error("render: generic textures wider than 16 channels are not supported");
     l.ch.n = o.num_channels; l.ch.max_generic = max_generic; l.ch.radiance_off = -1;
     l.ch.id = nullptr;                 // device copy made by render()
     l.ch.radiance_only = o.num_channels == 1 && o.channels[0] == RDR_CH_RADIANCE;

@@ -368,6 +368,12 @@ struct AdjBounceNee {
 // ---- adjoint of the camera vertex ------------------------------------------------------------------
 // Adjoint of the non-radiance G-buffer channels at the first hit: adds to the shading-point adjoint,
 // the ray-origin adjoint (depth) and the texture gradients (src/primary_contribution.cpp:487-700).
+// Upstream values of the generic channel, read from d_image as they are asked for (bsdf.h: adj_tex_fetch; any width).
+struct ImageBar {
+    const float *gi; double weight;
+    RDR_FN double operator()(int c) const { return weight * (double)gi[c]; }
+    RDR_FN const double *triple(double *o) const { o[0] = (*this)(0); o[1] = (*this)(1); o[2] = (*this)(2); return o; }
+};
 RDR_FN void adj_first_hit_channels(const SceneD &sc, const GScene &g, const ChannelsD &ch, const float *d_image,
                                    double weight, int p, int shape, const Surf &sp, const Ray &ray,
                                    Surf &pt_bar, V3 &org_bar) {
@@ -397,11 +403,8 @@ RDR_FN void adj_first_hit_channels(const SceneD &sc, const GScene &g, const Chan
             case 9: adj_tex3(m.specular, sp, weight * V3{(double)gi[d], (double)gi[d + 1], (double)gi[d + 2]}, gm.specular, pt_bar); break;
             case 10: adj_tex1(m.roughness, sp, weight * (double)gi[d], gm.roughness, pt_bar); break;
             case 11: {
-                if (m.generic.num_levels > 0) {
-                    double ob[kMaxGeneric];
-                    for (int j = 0; j < m.generic.channels; ++j) ob[j] = weight * (double)gi[d + j];
-                    adj_tex_fetch(m.generic, sp.uv, sp.du_dxy, sp.dv_dxy, ob, gm.generic, pt_bar.uv, pt_bar.du_dxy, pt_bar.dv_dxy);
-                }
+                if (m.generic.num_levels > 0)
+                    adj_tex_fetch(m.generic, sp.uv, sp.du_dxy, sp.dv_dxy, ImageBar{gi + d, weight}, gm.generic, pt_bar.uv, pt_bar.du_dxy, pt_bar.dv_dxy);
             } break;
             case 12: pt_bar.color += weight * V3{(double)gi[d], (double)gi[d + 1], (double)gi[d + 2]}; break;
             default: break;      // radiance handled by the caller; alpha and ids carry no gradient

@@ -94,8 +94,7 @@ RDR_FN rt::RayRec ray_rec(const Ray &r, bool dead) {
 RDR_FN void put_ray(rt::RayRec *q, int slot, const Ray &r, bool dead) { q[slot] = ray_rec(r, dead); }
 
 // Where a stage deposits radiance: the image (camera paths) and/or a per-lane scalar (edge paths).
-constexpr int kMaxChannels = 16;
-constexpr int kMaxGeneric = 16;      // widest generic texture the G-buffer channels accept
+constexpr int kMaxChannels = 16;     // entries of the channel list (a generic texture counts once, whatever its width)
 
 // Output channel list (src/channels.h:6-37): ids in request order, nd = total floats per pixel,
 // radiance_dim = offset of the radiance triple (-1 if not requested).
@@ -221,9 +220,9 @@ RDR_FN V3 direct_emission(const SceneD &sc, int shape, int tri, const Ray &ray, 
 // ---- stage: first-hit contribution -------------------------------------------------------------
 // Lanes: `active[idx]` (null = identity).  Records the hit ids of vertex `v` from queue slot idx.
 // Value of one non-radiance G-buffer channel at a first hit (src/primary_contribution.cpp:45-253).
-// Returns the number of components written to val (0: channel produces nothing here).
+// Returns the number of components written to val, at most 3 (0: channel produces nothing here).
 RDR_FN int channel_value(const SceneD &sc, int channel, const ShapeD &sh, const Surf &sp, const Ray &ray,
-                         int shape_id, int tri_id, int max_generic, double *val) {
+                         int shape_id, int tri_id, double *val) {
     const MaterialD &m = sc.materials[sh.material_id];
     switch (channel) {
         case 1: val[0] = 1; return 1;                                                   // alpha
@@ -240,11 +239,7 @@ RDR_FN int channel_value(const SceneD &sc, int channel, const ShapeD &sh, const 
         case 8: { V3 r = m.use_vertex_color ? sp.color : tex3(m.diffuse, sp); val[0] = r.x; val[1] = r.y; val[2] = r.z; return 3; }
         case 9: { V3 r = tex3(m.specular, sp); val[0] = r.x; val[1] = r.y; val[2] = r.z; return 3; }
         case 10: val[0] = tex1(m.roughness, sp); return 1;
-        case 11: {
-            if (m.generic.num_levels <= 0) return 0;
-            tex_fetch(m.generic, sp.uv, sp.du_dxy, sp.dv_dxy, val);
-            return m.generic.channels;
-        }
+        // (11, the generic texture, has no bound on its width: shade_first_hit streams its channels)
         case 12: val[0] = sp.color.x; val[1] = sp.color.y; val[2] = sp.color.z; return 3;
         case 13: val[0] = shape_id; return 1;
         case 14: val[0] = tri_id; return 1;
@@ -289,9 +284,26 @@ RDR_FN void shade_first_hit(const SceneD &sc, const Sink &sink, const VSlice &v,
                 px[0] += float(c.x); px[1] += float(c.y); px[2] += float(c.z);
             }
             if (sink.edge_contrib) sink.edge_contrib[p] += sum(c);
+        } else if (shape >= 0 && id == 11) {
+            // the generic texture: each channel's value goes to the image and into the edge estimator's sum as it is formed
+            const TexD &generic = sc.materials[sc.shapes[shape].material_id].generic;
+            float *px = sink.image ? sink.image + (size_t)sink.nd * p + d : nullptr;
+            const double *mul = sink.multipliers ? sink.multipliers + (size_t)sink.nd * p + d : nullptr;
+            const bool to_edge = sink.edge_contrib && mul;
+            double acc = 0;
+            if (generic.num_levels > 0)
+                tex_fetch_each(generic, sp.uv, sp.du_dxy, sp.dv_dxy, [&](int j, double val) {
+                    if (px) {
+                        double x = val * sink.weight;
+                        if (mul) x *= mul[j];
+                        px[j] += float(x);
+                    }
+                    if (to_edge) acc += (val * sink.weight) * mul[j];
+                });
+            if (to_edge) sink.edge_contrib[p] += acc;
         } else if (shape >= 0) {
-            double val[kMaxGeneric];
-            int nv = channel_value(sc, id, sc.shapes[shape], sp, ray, shape, tri, sink.ch.max_generic, val);
+            double val[3];
+            int nv = channel_value(sc, id, sc.shapes[shape], sp, ray, shape, tri, val);
             bool is_id = id >= 13;
             if (sink.image) {
                 float *px = sink.image + (size_t)sink.nd * p + d;
