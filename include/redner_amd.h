@@ -262,7 +262,22 @@ int rdr_compute_num_channels(const int *channels, int num_channels, int max_gene
  * CPU debugging harness accepts); with alpha the G-buffers must be 8-byte and the images 16-byte aligned.  The backward call
  * writes every element of d_g_buffer and d_light_params (no zero-filled buffers needed); the light gradients are summed in a
  * fixed order: bitwise reproducible from run to run.  Launches are ordered on the rdr_set_stream stream; both calls synchronise
- * before returning.  Return 0 on success. */
+ * before returning.  Return 0 on success.
+ *
+ * SHADOWS (not in the reference, whose render_deferred has none): with `occluders`, every texel of a shadowed image casts one
+ * any-hit shadow ray per light over the triangles of its occluder scene, and a light that is blocked adds nothing to the texel.
+ * The ray, in fp32 (csrc/deferred.h: shadow_ray): origin p, tmin = 1e-3f; point and spot: dir = (pos - p) / r with
+ * r = |pos - p|, tmax = (1 - 1e-3f) * r; directional: dir = -dir_l / |dir_l|, tmax = +inf; ambient lights cast none.  A ray is
+ * cast only where dir.n > 0 (for a spot also dir.s > 0), r > 0 and the record is finite; elsewhere the light counts as reaching
+ * the texel.  The texel is lit iff no triangle is hit in (tmin, tmax).
+ *   - A shadowed image may have at most 32 lights in its range (one bit each in the texel's visibility word): more is an error
+ *     that names the image and the count.
+ *   - A scene on another device than gpu_index, `occluders` without `visibility` and a `visibility` pointer that is not 4-byte
+ *     aligned are errors, raised before anything is launched.
+ *   - Visibility is a CONSTANT of the adjoint: rdr_deferred_shade_backward multiplies by the saved bits -- a light whose bit is 0
+ *     adds nothing to the texel's gradient nor to its own -- and produces no gradient across a shadow boundary (shadows are hard
+ *     and their edges are not differentiated).
+ * Both fields NULL (a zeroed tail): no shadows, the same launches and the same bits as before the fields existed. */
 enum rdr_deferred_light_type { RDR_DL_AMBIENT = 0, RDR_DL_POINT = 1, RDR_DL_DIRECTIONAL = 2, RDR_DL_SPOT = 3 };
 typedef struct rdr_deferred_desc {
     int num_images, height, width;      /* OUTPUT size */
@@ -271,6 +286,14 @@ typedef struct rdr_deferred_desc {
     const int32_t *light_type;          /* HOST [num_lights] */
     const int32_t *image_light_range;   /* HOST [num_images][2] */
     int gpu_index;
+    const rdr_scene *const *occluders;  /* HOST [num_images], or NULL: no shadows.  occluders[n] == NULL: image n is not
+                                           shadowed.  Every scene must live on device gpu_index (harness: host). */
+    uint32_t *visibility;               /* DEV [num_images][height * aa_samples][width * aa_samples], required iff
+                                           occluders != NULL (forward) / may be given alone (backward).  Bit b of a word: light
+                                           range[2n] + b reaches the texel.  rdr_deferred_shade writes every word;
+                                           rdr_deferred_shade_backward reads them and needs no scene.  Bits of ambient lights and
+                                           of lights that cast no ray at the texel are 1; bits at and above the length of the
+                                           image's range are 0. */
 } rdr_deferred_desc;
 int rdr_deferred_shade(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params, float *image);
 int rdr_deferred_shade_backward(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params,

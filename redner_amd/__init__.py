@@ -26,7 +26,8 @@
 import sys
 
 _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'DeferredShade',
-                 'deferred_shade', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo', 'render_pathtracing')
+                 'deferred_shade', 'occluder_scene', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo',
+                 'render_pathtracing')
 _TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid', 'envmap_sampling_tables')
 _UTILS = ('SH_reconstruct', 'SHReconstruct')
 _LOSS = ('gaussian_pyramid_loss', 'GaussianPyramidLoss')

@@ -19,7 +19,9 @@
 #pragma once
 #include "../../include/redner_amd.h"
 #include "arena.h"
+#include "scene.h"
 #include <cmath>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -100,6 +102,54 @@ RDR_DEV_FN void light_shade(int type, const float *lp, const Texel &t, float *rg
     }
     }
 }
+
+// ---- shadows: the ray a texel casts towards a light, and the texel's visibility word ------------------------------------------
+// THE RULE (fp32; the operands are the ones light_shade forms, the offsets the path tracer's: lights.h shadow_ray_to, camera.h
+// make_ray).  Origin p, tmin = 1e-3f and
+//   point, spot   d = pos - p, r = sqrtf(d.d):   dir = d / r,       tmax = (1 - 1e-3f) * r
+//   directional                                  dir = -D / |D|,    tmax = +inf
+//   ambient       no ray.
+// A ray is cast only if dir.n > 0, for a spot also dir.s > 0, r > 0, and every float of the record is finite (tmax of a
+// directional light: +inf by the rule above, nothing else).  Background texels (normal 0) therefore never cast, and a non-finite
+// ray never reaches the traversal kernels.  A texel is lit by the light iff the any-hit query finds no triangle in (tmin, tmax);
+// a texel that casts no ray counts as lit: light_shade decides (its cosine is <= 0 or NaN there).
+constexpr float kShadowOffset = 1e-3f;
+RDR_DEV_FN bool finite_f(float x) { return fabsf(x) <= 3.402823466e38f; }
+RDR_DEV_FN bool shadow_ray(int type, const float *lp, const Texel &t, rt::RayRec &rec) {
+    if (type == RDR_DL_AMBIENT) return false;
+    float dir[3], tmax;
+    if (type == RDR_DL_DIRECTIONAL) {
+        const float *D = lp + kDirection;
+        const float nd = sqrtf(dot3(D, D));
+        for (int k = 0; k < 3; ++k) dir[k] = -D[k] / nd;
+        tmax = INFINITY;
+    } else {
+        float d[3];
+        for (int k = 0; k < 3; ++k) d[k] = lp[kPosition + k] - t.p[k];
+        const float r = sqrtf(dot3(d, d));
+        if (!(r > 0.f)) return false;
+        for (int k = 0; k < 3; ++k) dir[k] = d[k] / r;
+        tmax = (1.f - kShadowOffset) * r;
+        if (!finite_f(tmax)) return false;
+        if (type == RDR_DL_SPOT) {
+            const float *D = lp + kDirection;
+            const float ns = sqrtf(dot3(D, D));
+            float s[3];
+            for (int k = 0; k < 3; ++k) s[k] = -D[k] / ns;
+            if (!(dot3(dir, s) > 0.f)) return false;
+        }
+    }
+    if (!(dot3(dir, t.n) > 0.f)) return false;
+    for (int k = 0; k < 3; ++k)
+        if (!finite_f(t.p[k]) || !finite_f(dir[k])) return false;
+    rec.ox = t.p[0]; rec.oy = t.p[1]; rec.oz = t.p[2]; rec.tmin = kShadowOffset;
+    rec.dx = dir[0]; rec.dy = dir[1]; rec.dz = dir[2]; rec.tmax = tmax;
+    return true;
+}
+// Bit b of a texel's word: light lb + b reaches the texel.  An image that is not shadowed may have more than 32 lights: those
+// beyond the word are lit.
+RDR_DEV_FN bool light_reaches(uint32_t word, int b) { return b >= 32 || ((word >> b) & 1u) != 0; }
+RDR_FN uint32_t full_mask(int len) { return len >= 32 ? 0xffffffffu : ((1u << len) - 1u); }
 
 // Adjoint of light_shade for the texel's upstream gradient w[3]: adds the texel's gradient to dt and, when PARAMS, the ten
 // parameter gradients to part.  (The two passes of the adjoint kernel each use one half; the other is dead code there.)
@@ -202,20 +252,32 @@ RDR_DEV_FN const float *texel_row(const View &v, int n, int y, int x, int ty) {
     const size_t hg = (size_t)v.height * v.aa, wg = (size_t)v.width * v.aa;
     return v.g + (((size_t)n * hg + (size_t)y * v.aa + ty) * wg + (size_t)x * v.aa) * C;
 }
+// ... and the visibility words of the same texels (one word per texel, whatever C is)
+RDR_DEV_FN const uint32_t *visibility_row(const View &v, const uint32_t *vis, int n, int y, int x, int ty) {
+    const size_t hg = (size_t)v.height * v.aa, wg = (size_t)v.width * v.aa;
+    return vis + ((size_t)n * hg + (size_t)y * v.aa + ty) * wg + (size_t)x * v.aa;
+}
 
 // One OUTPUT pixel of image n: shade its aa x aa texels by the lights [lb, le), average, write 3 | 4 floats.
-template <int C>
-RDR_DEV_FN void shade_pixel(const View &v, int n, int pix, int lb, int le, float *image) {
+// SHADOWED (here and in the two adjoint bodies): a light whose bit in the texel's word of `vis` is 0 is skipped; the plain
+// instantiation never looks at `vis` and is the code it was before there were shadows.
+template <int C, bool SHADOWED = false>
+RDR_DEV_FN void shade_pixel(const View &v, int n, int pix, int lb, int le, float *image, const uint32_t *vis = nullptr) {
     const int y = pix / v.width, x = pix - y * v.width;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int ty = 0; ty < v.aa; ++ty) {
         const float *row = texel_row<C>(v, n, y, x, ty);
+        const uint32_t *vrow = SHADOWED ? visibility_row(v, vis, n, y, x, ty) : nullptr;
         for (int tx = 0; tx < v.aa; ++tx) {
             Texel t;
             float alpha;
             load_texel<C>(row + tx * C, t, alpha);
             float rgb[3] = {0.f, 0.f, 0.f};
-            for (int l = lb; l < le; ++l) light_shade(v.type[l], v.params + (size_t)l * kLightParams, t, rgb);
+            const uint32_t word = SHADOWED ? vrow[tx] : 0u;
+            for (int l = lb; l < le; ++l) {
+                if (SHADOWED && !light_reaches(word, l - lb)) continue;
+                light_shade(v.type[l], v.params + (size_t)l * kLightParams, t, rgb);
+            }
             for (int k = 0; k < 3; ++k) acc[k] += rgb[k];
             acc[3] += alpha;
         }
@@ -245,21 +307,26 @@ RDR_DEV_FN void load_upstream(const View &v, int n, int pix, const float *d_imag
 }
 
 // Adjoint, pass 1: the gradient of every texel of one output pixel (each texel belongs to exactly one pixel: plain stores).
-template <int C>
-RDR_DEV_FN void adjoint_pixel_texels(const View &v, int n, int pix, int lb, int le, const float *d_image, float *d_g) {
+template <int C, bool SHADOWED = false>
+RDR_DEV_FN void adjoint_pixel_texels(const View &v, int n, int pix, int lb, int le, const float *d_image, float *d_g,
+                                     const uint32_t *vis = nullptr) {
     const int y = pix / v.width, x = pix - y * v.width;
     float w[4];
     load_upstream<C>(v, n, pix, d_image, w);
     for (int ty = 0; ty < v.aa; ++ty) {
         const float *row = texel_row<C>(v, n, y, x, ty);
         float *drow = d_g + (row - v.g);
+        const uint32_t *vrow = SHADOWED ? visibility_row(v, vis, n, y, x, ty) : nullptr;
         for (int tx = 0; tx < v.aa; ++tx) {
             Texel t, dt;
             float alpha;
             load_texel<C>(row + tx * C, t, alpha);
             for (int k = 0; k < 3; ++k) dt.p[k] = dt.n[k] = dt.a[k] = 0.f;
-            for (int l = lb; l < le; ++l)
+            const uint32_t word = SHADOWED ? vrow[tx] : 0u;
+            for (int l = lb; l < le; ++l) {
+                if (SHADOWED && !light_reaches(word, l - lb)) continue;
                 light_adjoint<false>(v.type[l], v.params + (size_t)l * kLightParams, t, w, dt, nullptr);
+            }
             float *o = drow + tx * C;
             if (C == 10) {
                 F2 *q = reinterpret_cast<F2 *>(o);
@@ -273,8 +340,9 @@ RDR_DEV_FN void adjoint_pixel_texels(const View &v, int n, int pix, int lb, int 
 }
 
 // Adjoint, pass 2: what one output pixel adds to the ten parameter gradients of light l.
-template <int C>
-RDR_DEV_FN void adjoint_pixel_light(const View &v, int n, int pix, int l, const float *d_image, double *part) {
+template <int C, bool SHADOWED = false>
+RDR_DEV_FN void adjoint_pixel_light(const View &v, int n, int pix, int l, const float *d_image, double *part,
+                                    const uint32_t *vis = nullptr, int lb = 0) {
     const int y = pix / v.width, x = pix - y * v.width;
     float w[4];
     load_upstream<C>(v, n, pix, d_image, w);
@@ -282,7 +350,9 @@ RDR_DEV_FN void adjoint_pixel_light(const View &v, int n, int pix, int l, const 
     const float *lp = v.params + (size_t)l * kLightParams;
     for (int ty = 0; ty < v.aa; ++ty) {
         const float *row = texel_row<C>(v, n, y, x, ty);
+        const uint32_t *vrow = SHADOWED ? visibility_row(v, vis, n, y, x, ty) : nullptr;
         for (int tx = 0; tx < v.aa; ++tx) {
+            if (SHADOWED && !light_reaches(vrow[tx], l - lb)) continue;
             Texel t, dt;
             float alpha;
             load_texel<C>(row + tx * C, t, alpha);
@@ -295,14 +365,16 @@ RDR_DEV_FN void adjoint_pixel_light(const View &v, int n, int pix, int l, const 
 #if !defined(RDR_HOSTSIM)
 // ---- gfx950 kernels --------------------------------------------------------------------------------------------------------
 // grid = (blocks per image, N): the light range of a block is uniform, so the table is read through scalar loads.
-template <int C>
+template <int C, bool SHADOWED>
 __global__ void __launch_bounds__(256) deferred_shade_kernel(const float *__restrict__ g, const float *__restrict__ params,
                                                              const int *__restrict__ type, const int *__restrict__ range, int height,
-                                                             int width, int aa, float *__restrict__ image) {
+                                                             int width, int aa, float *__restrict__ image,
+                                                             const uint32_t *__restrict__ vis) {
     const View v{g, params, type, range, height, width, aa};
     const int n = blockIdx.y, pixels = v.height * v.width;
     const int lb = v.range[2 * n], le = v.range[2 * n + 1];
-    for (int pix = blockIdx.x * 256 + threadIdx.x; pix < pixels; pix += gridDim.x * 256) shade_pixel<C>(v, n, pix, lb, le, image);
+    for (int pix = blockIdx.x * 256 + threadIdx.x; pix < pixels; pix += gridDim.x * 256)
+        shade_pixel<C, SHADOWED>(v, n, pix, lb, le, image, vis);
 }
 
 // The grid is capped (kAdjointBlocks) and strides over the pixels.  Pass 1 writes the texel gradients.  Pass 2 loops over the
@@ -311,23 +383,26 @@ __global__ void __launch_bounds__(256) deferred_shade_kernel(const float *__rest
 // the wave (DPP), across the four waves through LDS, and the block writes
 // ONE row of the slab [blocks][slab_stride]: no atomics, and a fixed summation order (deferred_fold_kernel).
 constexpr int kAdjointBlocks = 2048;
-template <int C>
+template <int C, bool SHADOWED>
 __global__ void __launch_bounds__(256, 4) deferred_adjoint_kernel(const float *__restrict__ g, const float *__restrict__ params,
                                                                const int *__restrict__ type, const int *__restrict__ range, int height,
                                                                int width, int aa, const float *__restrict__ d_image,
-                                                               float *__restrict__ d_g, double *__restrict__ slab, int slab_stride) {
+                                                               float *__restrict__ d_g, double *__restrict__ slab, int slab_stride,
+                                                               const uint32_t *__restrict__ vis) {
     // (the tables as `restrict` arguments: the stores of pass 1 cannot alias them, so their loads stay scalar)
     const View v{g, params, type, range, height, width, aa};
     const int n = blockIdx.y, pixels = v.height * v.width;
     const int lb = v.range[2 * n], le = v.range[2 * n + 1];
     const int first = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
-    for (int pix = first; pix < pixels; pix += step) adjoint_pixel_texels<C>(v, n, pix, lb, le, d_image, d_g);
+    for (int pix = first; pix < pixels; pix += step)
+        adjoint_pixel_texels<C, SHADOWED>(v, n, pix, lb, le, d_image, d_g, vis);
     __shared__ double wave_part[4][kLightParams];
     double *row = slab + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * slab_stride;
     for (int l = lb; l < le; ++l) {
         double part[kLightParams];
         for (int k = 0; k < kLightParams; ++k) part[k] = 0.0;
-        for (int pix = first; pix < pixels; pix += step) adjoint_pixel_light<C>(v, n, pix, l, d_image, part);
+        for (int pix = first; pix < pixels; pix += step)
+            adjoint_pixel_light<C, SHADOWED>(v, n, pix, l, d_image, part, vis, lb);
         for (int k = 0; k < kLightParams; ++k) part[k] = wave_sum(part[k]);         // every lane is active here
         if ((threadIdx.x & 63) == 0)
             for (int k = 0; k < kLightParams; ++k) wave_part[threadIdx.x >> 6][k] = part[k];
@@ -407,22 +482,115 @@ inline View make_view(const rdr_deferred_desc &d, const Tables &t, const float *
     return View{g, params, t.dev, t.dev + d.num_lights, d.height, d.width, d.aa_samples};
 }
 
+// ---- shadows: the visibility words of a call (stages on exec::launch: kernels on the GPU, plain loops in the harness) ---------
+// One pass per (shadowed image, ray-casting light, chunk of at most kShadowChunk texels), all on the call's stream:
+//   compact_dev   the texels of the chunk that cast a ray by the rule -> list; the count stays on the device
+//   ShadowRays    one lane per listed texel: the 32-byte record as two 16-byte stores
+//   exec::trace   any-hit over the occluder scene's hierarchy, trimmed by the device's count
+//   ShadowMark    one lane per listed texel: a hit clears the light's bit.  Within a pass a word has one owner, and passes are
+//                 ordered by the stream: a plain read-modify-write.
+// The host reads no count back, and the scratch (list 4 + rays 32 + hits 8 bytes per texel of a chunk) does not grow with the
+// number of lights.
+constexpr int kShadowChunk = 1 << 22;
+// RDR_DEFERRED_SHADOW_CHUNK: a smaller chunk (tests: a pass split into several chunks gives the same words)
+inline int shadow_chunk() {
+    const char *e = std::getenv("RDR_DEFERRED_SHADOW_CHUNK");
+    const long v = e ? std::atol(e) : 0;
+    return v > 0 && v < kShadowChunk ? (int)v : kShadowChunk;
+}
+
+struct FillWords {
+    uint32_t *words; uint32_t value;
+    RDR_DEV_FN void operator()(int i) const { words[i] = value; }
+};
+// `texels`: the first texel of the chunk; `lp`: the light's ten parameters (uniform: scalar loads)
 template <int C>
-inline void shade_impl(const rdr_deferred_desc &d, const View &v, float *image) {
+struct CastsShadowRay {
+    const float *texels; int type; const float *lp;
+    RDR_DEV_FN bool operator()(int i) const {
+        Texel t;
+        float alpha;
+        load_texel<C>(texels + (size_t)i * C, t, alpha);
+        rt::RayRec rec;
+        return shadow_ray(type, lp, t, rec);
+    }
+};
+template <int C>
+struct ShadowRays {
+    const float *texels; int type; const float *lp; const int *list; rt::RayRec *queue;
+    RDR_DEV_FN void operator()(int slot) const {
+        Texel t;
+        float alpha;
+        load_texel<C>(texels + (size_t)list[slot] * C, t, alpha);
+        rt::RayRec rec;
+        if (!shadow_ray(type, lp, t, rec)) {         // (the list holds only texels that cast; a moot ray all the same)
+            rec.ox = rec.oy = rec.oz = rec.tmin = rec.dx = rec.dy = rec.dz = 0.f;
+            rec.tmax = -1.f;
+        }
+        F4 *out = reinterpret_cast<F4 *>(queue + slot);
+        out[0] = F4{rec.ox, rec.oy, rec.oz, rec.tmin};
+        out[1] = F4{rec.dx, rec.dy, rec.dz, rec.tmax};
+    }
+};
+struct ShadowMark {
+    const int *list; const rt::HitRec *hits; uint32_t *words; uint32_t bit;
+    RDR_DEV_FN void operator()(int slot) const {
+        if (hits[slot].shape >= 0) words[list[slot]] &= ~bit;
+    }
+};
+
+template <int C>
+inline void cast_shadows(const rdr_deferred_desc &d, const View &v, uint32_t *vis, Arena &arena) {
+    const size_t texels = (size_t)d.height * d.aa_samples * (size_t)d.width * d.aa_samples;       // validate: at most 2e8
+    const int chunk = texels < (size_t)shadow_chunk() ? (int)texels : shadow_chunk();
+    int *list = nullptr;
+    rt::RayRec *queue = nullptr;
+    rt::HitRec *hits = nullptr;
+    for (int n = 0; n < d.num_images; ++n) {
+        const int lb = d.image_light_range[2 * n], le = d.image_light_range[2 * n + 1];
+        uint32_t *words = vis + (size_t)n * texels;
+        exec::launch((int)texels, FillWords{words, full_mask(le - lb)});
+        if (!d.occluders[n]) continue;
+        const Scene &scene = *reinterpret_cast<const Scene *>(d.occluders[n]);
+        for (int l = lb; l < le; ++l) {
+            const int type = d.light_type[l];
+            if (type == RDR_DL_AMBIENT) continue;
+            if (!list) {
+                list = arena.get<int>((size_t)chunk);
+                queue = arena.get<rt::RayRec>((size_t)chunk);
+                hits = arena.get<rt::HitRec>((size_t)chunk);
+            }
+            const float *lp = v.params + (size_t)l * kLightParams;
+            for (size_t base = 0; base < texels; base += (size_t)chunk) {
+                const int count = texels - base < (size_t)chunk ? (int)(texels - base) : chunk;
+                const float *first = v.g + ((size_t)n * texels + base) * C;
+                const exec::Count live = exec::compact_dev(nullptr, exec::Count(count), list, CastsShadowRay<C>{first, type, lp});
+                exec::launch(live, ShadowRays<C>{first, type, lp, list, queue});
+                exec::trace(scene.bvh, queue, hits, live, true);
+                exec::launch(live, ShadowMark{list, hits, words + base, 1u << (l - lb)});
+            }
+        }
+    }
+}
+
+template <int C, bool SHADOWED>
+inline void shade_impl(const rdr_deferred_desc &d, const View &v, float *image, const uint32_t *vis) {
     const int pixels = d.height * d.width;
 #if !defined(RDR_HOSTSIM)
     const dim3 grid((pixels + 255) / 256, d.num_images);
-    hipLaunchKernelGGL(deferred_shade_kernel<C>, grid, dim3(256), 0, exec::ctx().stream, v.g, v.params, v.type, v.range,
-                       v.height, v.width, v.aa, image);
+    hipLaunchKernelGGL((deferred_shade_kernel<C, SHADOWED>), grid, dim3(256), 0, exec::ctx().stream, v.g, v.params, v.type, v.range,
+                       v.height, v.width, v.aa, image, vis);
     exec::check(hipGetLastError(), "deferred_shade launch");
 #else
     for (int n = 0; n < d.num_images; ++n)
-        for (int pix = 0; pix < pixels; ++pix) shade_pixel<C>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], image);
+        for (int pix = 0; pix < pixels; ++pix)
+            shade_pixel<C, SHADOWED>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], image, vis);
 #endif
 }
 
-template <int C>
-inline void adjoint_impl(const rdr_deferred_desc &d, const View &v, const float *d_image, float *d_g, float *d_params) {
+template <int C, bool SHADOWED>
+inline void adjoint_impl(const rdr_deferred_desc &d, const View &v, const float *d_image, float *d_g, float *d_params,
+                         const uint32_t *vis) {
     const int pixels = d.height * d.width;
 #if !defined(RDR_HOSTSIM)
     int per_image = (pixels + 255) / 256;
@@ -436,8 +604,8 @@ inline void adjoint_impl(const rdr_deferred_desc &d, const View &v, const float 
     const int slab_stride = longest * kLightParams;
     Arena arena;
     double *slab = arena.get<double>((size_t)per_image * d.num_images * (slab_stride > 0 ? slab_stride : 1));
-    hipLaunchKernelGGL(deferred_adjoint_kernel<C>, dim3(per_image, d.num_images), dim3(256), 0, exec::ctx().stream, v.g, v.params,
-                       v.type, v.range, v.height, v.width, v.aa, d_image, d_g, slab, slab_stride);
+    hipLaunchKernelGGL((deferred_adjoint_kernel<C, SHADOWED>), dim3(per_image, d.num_images), dim3(256), 0, exec::ctx().stream, v.g,
+                       v.params, v.type, v.range, v.height, v.width, v.aa, d_image, d_g, slab, slab_stride, vis);
     exec::check(hipGetLastError(), "deferred_shade_adjoint launch");
     if (d.num_lights > 0) {
         hipLaunchKernelGGL(deferred_fold_kernel, dim3(d.num_lights), dim3(256), 0, exec::ctx().stream, slab, slab_stride, per_image,
@@ -447,16 +615,39 @@ inline void adjoint_impl(const rdr_deferred_desc &d, const View &v, const float 
     exec::upload_flush();              // the stream is drained before the slab goes back to the pool
 #else
     for (int n = 0; n < d.num_images; ++n)
-        for (int pix = 0; pix < pixels; ++pix) adjoint_pixel_texels<C>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], d_image, d_g);
+        for (int pix = 0; pix < pixels; ++pix)
+            adjoint_pixel_texels<C, SHADOWED>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], d_image, d_g, vis);
     for (int l = 0; l < d.num_lights; ++l) {
         double part[kLightParams] = {0};
         for (int n = 0; n < d.num_images; ++n) {
             if (l < v.range[2 * n] || l >= v.range[2 * n + 1]) continue;
-            for (int pix = 0; pix < pixels; ++pix) adjoint_pixel_light<C>(v, n, pix, l, d_image, part);
+            for (int pix = 0; pix < pixels; ++pix) adjoint_pixel_light<C, SHADOWED>(v, n, pix, l, d_image, part, vis, v.range[2 * n]);
         }
         for (int k = 0; k < kLightParams; ++k) d_params[l * kLightParams + k] = (float)part[k];
     }
 #endif
+}
+
+// What the two shadow fields of the description ask for, checked before anything is launched.  `forward`: the words are written
+// (occluders and visibility come together); backward: the words are read and no scene is looked at.
+inline void validate_shadows(const rdr_deferred_desc &d, bool forward, const char *who) {
+    auto fail = [&](const std::string &what) { throw std::runtime_error(std::string(who) + ": " + what); };
+    if (forward && d.occluders && !d.visibility) fail("occluders need a visibility buffer");
+    if (forward && !d.occluders && d.visibility) fail("a visibility buffer needs occluders");
+    if (d.visibility && ((uintptr_t)d.visibility & 3)) fail("the visibility buffer must be 4-byte aligned");
+    if (!forward || !d.occluders) return;
+    for (int n = 0; n < d.num_images; ++n) {
+        if (!d.occluders[n]) continue;
+        const int len = d.image_light_range[2 * n + 1] - d.image_light_range[2 * n];
+        if (len > 32)
+            fail("shadowed image " + std::to_string(n) + " has " + std::to_string(len) + " lights, at most 32 fit its visibility word");
+#if !defined(RDR_HOSTSIM)
+        const int at = reinterpret_cast<const Scene *>(d.occluders[n])->gpu_index;
+        if (at != d.gpu_index)
+            fail("the occluder scene of image " + std::to_string(n) + " lives on device " + std::to_string(at) +
+                 ", the call runs on device " + std::to_string(d.gpu_index));
+#endif
+    }
 }
 
 // rdr_deferred_shade: synchronised on return
@@ -465,13 +656,22 @@ inline void shade(const rdr_deferred_desc &d, const float *g, const float *param
     if (!g || !image || (d.num_lights > 0 && !params)) throw std::runtime_error("rdr_deferred_shade: null tensor");
     if (d.alpha && (((uintptr_t)g & 7) || ((uintptr_t)image & 15)))
         throw std::runtime_error("rdr_deferred_shade: with alpha the G-buffer must be 8-byte and the image 16-byte aligned");
+    validate_shadows(d, true, "rdr_deferred_shade");
     Tables tables(d);
     const View v = make_view(d, tables, g, params);
-    if (d.alpha) shade_impl<10>(d, v, image); else shade_impl<9>(d, v, image);
+    if (d.occluders) {
+        Arena scratch;                     // back in the pool after the upload_flush below
+        if (d.alpha) { cast_shadows<10>(d, v, d.visibility, scratch); shade_impl<10, true>(d, v, image, d.visibility); }
+        else { cast_shadows<9>(d, v, d.visibility, scratch); shade_impl<9, true>(d, v, image, d.visibility); }
+        exec::upload_flush();
+        return;
+    }
+    if (d.alpha) shade_impl<10, false>(d, v, image, nullptr); else shade_impl<9, false>(d, v, image, nullptr);
     exec::upload_flush();
 }
 
-// rdr_deferred_shade_backward: synchronised on return
+// rdr_deferred_shade_backward: synchronised on return.  Visibility is a constant of the adjoint: a light whose bit is 0 adds
+// nothing to the texel's gradient nor to its own.
 inline void shade_backward(const rdr_deferred_desc &d, const float *g, const float *params, const float *d_image, float *d_g,
                            float *d_params) {
     validate(d, "rdr_deferred_shade_backward");
@@ -479,9 +679,15 @@ inline void shade_backward(const rdr_deferred_desc &d, const float *g, const flo
         throw std::runtime_error("rdr_deferred_shade_backward: null tensor");
     if (d.alpha && ((((uintptr_t)g | (uintptr_t)d_g) & 7) || ((uintptr_t)d_image & 15)))
         throw std::runtime_error("rdr_deferred_shade_backward: with alpha the G-buffers must be 8-byte and the image gradient 16-byte aligned");
+    validate_shadows(d, false, "rdr_deferred_shade_backward");
     Tables tables(d);
     const View v = make_view(d, tables, g, params);
-    if (d.alpha) adjoint_impl<10>(d, v, d_image, d_g, d_params); else adjoint_impl<9>(d, v, d_image, d_g, d_params);
+    const uint32_t *vis = d.visibility;
+    if (vis) {
+        if (d.alpha) adjoint_impl<10, true>(d, v, d_image, d_g, d_params, vis); else adjoint_impl<9, true>(d, v, d_image, d_g, d_params, vis);
+    } else {
+        if (d.alpha) adjoint_impl<10, false>(d, v, d_image, d_g, d_params, nullptr); else adjoint_impl<9, false>(d, v, d_image, d_g, d_params, nullptr);
+    }
     exec::upload_flush();
 }
 

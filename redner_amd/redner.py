@@ -418,7 +418,8 @@ class DeferredLightType(enum.IntEnum):     # rdr_deferred_light_type (not in the
     spot = _capi.DL_SPOT
 
 
-def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index):
+def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
+                   occluders=None, visibility=None):
     d = _capi.DeferredDesc()
     d.num_images, d.height, d.width = int(num_images), int(height), int(width)
     d.aa_samples, d.alpha, d.num_lights = int(aa_samples), int(bool(alpha)), len(light_types)
@@ -429,23 +430,41 @@ def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, im
     ranges = (C.c_int32 * max(len(flat), 1))(*flat)
     d.light_type, d.image_light_range = types, ranges
     d.gpu_index = _gpu_index(use_gpu, gpu_index)
-    return d, (types, ranges)
+    handles = None
+    if occluders is not None:              # one Scene (or None: not shadowed) per image; the table lives as long as the call
+        occluders = list(occluders)
+        if len(occluders) != d.num_images:
+            raise RuntimeError('redner.deferred_shade: %d occluder scenes for %d images' % (len(occluders), d.num_images))
+        lib = _capi.lib()
+        for sc in occluders:
+            if sc is not None and (not isinstance(sc, Scene) or sc._handle is None or sc._lib is not lib):
+                raise RuntimeError('redner.deferred_shade: an occluder must be a live Scene of the loaded library, or None')
+        handles = (C.c_void_p * max(len(occluders), 1))(*[None if sc is None else sc._handle for sc in occluders])
+        d.occluders = handles
+    if visibility is not None:
+        d.visibility = _ptr(visibility)
+    return d, (types, ranges, handles, occluders)
 
 
 def deferred_shade(g_buffer, light_params, image, num_images, height, width, aa_samples, alpha, light_types,
-                   image_light_ranges, use_gpu, gpu_index):
+                   image_light_ranges, use_gpu, gpu_index, occluders=None, visibility=None):
     """Not in the reference: rdr_deferred_shade (include/redner_amd.h).  g_buffer [N, H * aa, W * aa, 9 + alpha],
     light_params [L, 10], image [N, H, W, 3 + alpha]: float_ptr; light_types: L DeferredLightType; image_light_ranges: N
-    (begin, end) pairs into the table."""
-    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index)
+    (begin, end) pairs into the table.  Shadows: `occluders`, N Scenes (None: that image is not shadowed), and `visibility`,
+    int_ptr to [N, H * aa, W * aa] 32-bit words, every one of which is written (bit b: light begin + b reaches the texel)."""
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
+                              occluders, visibility)
     _call(_capi.lib(), 'deferred_shade', 'rdr_deferred_shade', C.byref(d), _ptr(g_buffer), _ptr(light_params), _ptr(image),
           on=(use_gpu, gpu_index))
 
 
 def deferred_shade_backward(g_buffer, light_params, d_image, d_g_buffer, d_light_params, num_images, height, width,
-                            aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index):
-    """Not in the reference: rdr_deferred_shade_backward; writes every element of d_g_buffer and d_light_params."""
-    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index)
+                            aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index, occluders=None,
+                            visibility=None):
+    """Not in the reference: rdr_deferred_shade_backward; writes every element of d_g_buffer and d_light_params.  `visibility`:
+    the words the forward call wrote, held constant (no scene is needed)."""
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
+                              occluders, visibility)
     _call(_capi.lib(), 'deferred_shade_backward', 'rdr_deferred_shade_backward', C.byref(d), _ptr(g_buffer), _ptr(light_params),
           _ptr(d_image), _ptr(d_g_buffer), _ptr(d_light_params), on=(use_gpu, gpu_index))
 

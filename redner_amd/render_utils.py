@@ -22,6 +22,10 @@ Per G-buffer texel with position p, normal n, albedo a, summed over the lights (
                                                       I * pow(max(l.s, 0), e) * max(l.n, 0) * (a / pi)
 
 then alpha appended unshaded and the mean over each aa x aa block.
+
+Shadows (`render_deferred(..., shadows=True)`, `deferred_shade(..., occluders=...)`; not in the reference): every texel casts one
+any-hit shadow ray per point, spot and directional light over the scene's triangles, on the path tracer's traversal kernels and
+with its 1e-3 offsets; a blocked light adds nothing to the texel.  Shadows are hard, and visibility is a constant of the gradient.
 """
 import random
 from typing import List, Optional, Union
@@ -134,10 +138,12 @@ def _aligned(t, alpha):
 
 class DeferredShade(torch.autograd.Function):
     """apply(g_buffer [N, H * aa, W * aa, 9 + alpha], light_params [L, 10], light_types, image_light_ranges, aa_samples, alpha,
-    backend) -> [N, H, W, 3 + alpha].  One native launch forward, one (+ the fold of the light gradients) backward."""
+    backend, occluders) -> [N, H, W, 3 + alpha].  One native launch forward, one (+ the fold of the light gradients) backward.
+    `occluders`: None, or N `backend.Scene` (None: that image is not shadowed) -- the shadow rays of the forward call are traced
+    over them; the [N, H * aa, W * aa] visibility words are saved for the backward call, which needs no scene."""
 
     @staticmethod
-    def forward(ctx, g_buffer, light_params, light_types, image_light_ranges, aa_samples, alpha, backend=None):
+    def forward(ctx, g_buffer, light_params, light_types, image_light_ranges, aa_samples, alpha, backend=None, occluders=None):
         rd = backend or _default_backend
         light_types = tuple(int(t) for t in light_types)
         image_light_ranges = tuple((int(b), int(e)) for b, e in image_light_ranges)
@@ -155,6 +161,8 @@ class DeferredShade(torch.autograd.Function):
                                % (len(light_types), _LIGHT_PARAMS, tuple(light_params.shape)))
         if len(image_light_ranges) != n:
             raise RuntimeError('DeferredShade: %d light ranges for %d images' % (len(image_light_ranges), n))
+        if occluders is not None and len(occluders) != n:
+            raise RuntimeError('DeferredShade: %d occluder scenes for %d images' % (len(occluders), n))
         if g_buffer.dtype != torch.float32 or light_params.dtype != torch.float32:
             raise RuntimeError('DeferredShade: fp32 tensors only')
         device = g_buffer.device
@@ -164,27 +172,65 @@ class DeferredShade(torch.autograd.Function):
         h, w = hg // aa_samples, wg // aa_samples
         image = torch.empty(n, h, w, 3 + int(alpha), dtype=torch.float32, device=device)
         geometry = (n, h, w, aa_samples, alpha, light_types, image_light_ranges, use_gpu, index)
-        rd.deferred_shade(ptr(rd, g), ptr(rd, params), ptr(rd, image), *geometry)
         ctx.rd, ctx.geometry, ctx.params_device = rd, geometry, light_params.device
-        ctx.save_for_backward(g, params)
-        return image
+        if occluders is None:
+            rd.deferred_shade(ptr(rd, g), ptr(rd, params), ptr(rd, image), *geometry)
+            ctx.shadowed = False
+            ctx.save_for_backward(g, params)
+            return image
+        visibility = torch.empty(n, hg, wg, dtype=torch.int32, device=device)        # every word is written
+        rd.deferred_shade(ptr(rd, g), ptr(rd, params), ptr(rd, image), *geometry, occluders=tuple(occluders),
+                          visibility=rd.int_ptr(visibility.data_ptr()))
+        ctx.shadowed = True
+        ctx.save_for_backward(g, params, visibility)
+        ctx.mark_non_differentiable(visibility)
+        return image, visibility
 
     @staticmethod
-    def backward(ctx, grad_img):
+    def backward(ctx, grad_img, grad_visibility=None):
         rd, geometry = ctx.rd, ctx.geometry
-        g, params = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        g, params = saved[0], saved[1]
         alpha = geometry[4]
         grad_img = _aligned(upstream(grad_img, g.device), alpha)
         assert torch.isfinite(grad_img).all()
         d_g = torch.empty_like(g)
         d_params = torch.empty_like(params)
-        rd.deferred_shade_backward(ptr(rd, g), ptr(rd, params), ptr(rd, grad_img), ptr(rd, d_g), ptr(rd, d_params), *geometry)
-        return d_g, d_params.to(ctx.params_device), None, None, None, None, None
+        if ctx.shadowed:
+            rd.deferred_shade_backward(ptr(rd, g), ptr(rd, params), ptr(rd, grad_img), ptr(rd, d_g), ptr(rd, d_params), *geometry,
+                                       visibility=rd.int_ptr(saved[2].data_ptr()))
+        else:
+            rd.deferred_shade_backward(ptr(rd, g), ptr(rd, params), ptr(rd, grad_img), ptr(rd, d_g), ptr(rd, d_params), *geometry)
+        return d_g, d_params.to(ctx.params_device), None, None, None, None, None, None
 
 
-def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None):
+class OccluderScene:
+    """What `occluder_scene` returns: the `backend.Scene` whose triangle hierarchy the shadow rays are traced over, together with
+    the tensors its handle points into."""
+
+    def __init__(self, scene, keep):
+        self.scene, self._keep = scene, keep
+
+
+def occluder_scene(scene, device: Optional[torch.device] = None, backend=None):
+    """The triangles of `scene` as `deferred_shade(occluders=...)` takes them, for users who shade their own G-buffers.  Built as
+    a render would build it, without the edge-sampling structures (shadow boundaries are not differentiated); for geometry the
+    library has seen before, the topology caches make this a refit or a share."""
+    backend = backend or _default_backend
+    device = _default_device(device)
+    args = RenderFunction.serialize_scene(scene, (1, 1), 0, channels=[backend.channels.position],
+                                          sampler_type=backend.SamplerType.sobol, use_primary_edge_sampling=False,
+                                          use_secondary_edge_sampling=False, device=device, backend=backend)
+    u = RenderFunction.unpack_args((0, 0), args[0], args[1:])
+    return OccluderScene(u.scene, (u, args))
+
+
+def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None, occluders=None, return_visibility=False):
     """Shade a stack of G-buffers [N, H * aa, W * aa, 9 + alpha] in one launch.  `lights`: one list of DeferredLight shared by
-    the N images, or N lists."""
+    the N images, or N lists.  `occluders`: None (no shadows), one `occluder_scene(...)` for all images, or a list of N of them
+    (None: that image is not shadowed); a shadowed image may have at most 32 lights.  Shadows are hard and are held constant by
+    the gradient.  `return_visibility`: also the [N, H * aa, W * aa] int32 words, bit b = light b of the image's list reaches the
+    texel (all lights, when there are no occluders)."""
     n = int(g_buffer.shape[0])
     per_image = len(lights) > 0 and isinstance(lights[0], (list, tuple))
     if per_image:
@@ -197,7 +243,15 @@ def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None):
     else:
         flat, ranges = list(lights), [(0, len(lights))] * n
     params, types = pack_lights(flat, g_buffer.device)
-    return DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend)
+    if occluders is None and not return_visibility:
+        return DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend)
+    if occluders is None or not isinstance(occluders, (list, tuple)):
+        occluders = [occluders] * n
+    elif len(occluders) != n:
+        raise RuntimeError('render_deferred: %d occluder scenes for %d images' % (len(occluders), n))
+    scenes = tuple(o.scene if isinstance(o, OccluderScene) else o for o in occluders)        # (`occluders` lives through the call)
+    image, visibility = DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend, scenes)
+    return (image, visibility) if return_visibility else image
 
 
 def _default_device(device):
@@ -238,13 +292,18 @@ def _render_g_buffer_for_deferred(scene, seed, channels, aa_samples, sample_pixe
 
 def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = False, aa_samples: int = 2, seed=None,
                     sample_pixel_center: bool = False, use_primary_edge_sampling: bool = True,
-                    device: Optional[torch.device] = None, backend=None):
-    """Deferred rendering: Lambertian shading of the G-buffer by `lights`, no shadows.
+                    device: Optional[torch.device] = None, backend=None, shadows: bool = False):
+    """Deferred rendering: Lambertian shading of the G-buffer by `lights`.
 
     scene: a Scene -> [H, W, 3 | 4]; a list of N scenes of one resolution -> [N, H, W, 3 | 4], shaded in one launch.
     lights: a list of DeferredLight (shared by all scenes of a batch) or, for a batch, one list per scene.
     seed: an int (a list of N ints for a batch); random when None.
-    `backend` (redner_amd extension): the module providing the `redner` API, as for RenderFunction.serialize_scene."""
+    `backend` (redner_amd extension): the module providing the `redner` API, as for RenderFunction.serialize_scene.
+    `shadows` (redner_amd extension; the reference's render_deferred has none): every texel casts one any-hit shadow ray per
+    point, spot and directional light over the triangles of its scene, with the path tracer's offsets (the ray starts 1e-3 along
+    its direction and, for a light with a position, ends at (1 - 1e-3) of the distance); a light that is blocked adds nothing.
+    Shadows are HARD and are not differentiated across their boundary: the gradient holds visibility constant (DESIGN.md
+    section 7).  At most 32 lights per scene."""
     backend = backend or _default_backend
     device = _default_device(device)
     aa_samples = int(aa_samples)
@@ -259,7 +318,9 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
     g_buffers = [_render_g_buffer_for_deferred(sc, se, channels, aa_samples, sample_pixel_center, use_primary_edge_sampling,
                                                device, backend) for sc, se in zip(scenes, seeds)]
     g_buffer = g_buffers[0].unsqueeze(0) if single else torch.stack(g_buffers)
-    images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend)
+    # (the occluder scenes live until the shade call has returned)
+    occluders = [occluder_scene(sc, device=device, backend=backend) for sc in scenes] if shadows else None
+    images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend, occluders=occluders)
     return images[0] if single else images
 
 
