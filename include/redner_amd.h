@@ -258,6 +258,19 @@ int rdr_compute_num_channels(const int *channels, int num_channels, int max_gene
  *   point        d = pos - p, l = d / |d|:            I * max(l.n, 0) * (a / pi) / d.d
  *   directional  l = -dir / |dir|:                    I * max(l.n, 0) * (a / pi)
  *   spot         l = (pos - p) / |pos - p|, s = -sdir / |sdir|:   I * pow(max(l.s, 0), e) * max(l.n, 0) * (a / pi)
+ * SH ROWS (RDR_DL_SH_R, _G, _B; not in the reference): a row lights ONE colour channel c by a spherical-harmonic environment.
+ * light_params[l][0..8] are the nine coefficients k_i of that channel in the order i = l*l + l + m of rdr_sh_reconstruct
+ * (l = 0..2, m = -l..l); [9] is unused and its gradient is 0.  The basis and the directions are those of rdr_sh_reconstruct
+ * and an environment map with identity env_to_world (the map's texel at (theta, phi) lies in world direction
+ * (sin phi sin theta, cos theta, -cos phi sin theta)); there is no rotation of the SH frame.  With the normal as stored,
+ * x = -n.z, y = n.x, z = n.y:
+ *   Y0 = 0.28209479   Y1 = -0.48860251 y   Y2 = 0.48860251 z   Y3 = -0.48860251 x   Y4 = 1.09254843 x y   Y5 = -1.09254843 y z
+ *   Y6 = 0.31539157 (3 z z - 1)   Y7 = -1.09254843 x z   Y8 = 0.54627422 (x x - y y)
+ *   E = sum_i A_i k_i Y_i,  A = pi (l = 0), 2 pi / 3 (l = 1), pi / 4 (l = 2);   the row adds  max(E, 0) * a_c / pi  to channel c.
+ * fp32, the sum in ascending i (csrc/deferred.h states the order of every operation).  At E == 0 exactly the clamp passes half
+ * the gradient, like every max(x, 0) here: all-zero coefficients receive a gradient.  The position takes no part (its gradient
+ * from an SH row is exactly 0).  A light with three colour channels is three consecutive rows (the Python SHLight); each row
+ * is meaningful alone.
  * g_buffer, light_params, image, d_* are DEV pointers on device gpu_index (a negative gpu_index: host memory, which only the
  * CPU debugging harness accepts); with alpha the G-buffers must be 8-byte and the images 16-byte aligned.  The backward call
  * writes every element of d_g_buffer and d_light_params (no zero-filled buffers needed); the light gradients are summed in a
@@ -267,18 +280,20 @@ int rdr_compute_num_channels(const int *channels, int num_channels, int max_gene
  * SHADOWS (not in the reference, whose render_deferred has none): with `occluders`, every texel of a shadowed image casts one
  * any-hit shadow ray per light over the triangles of its occluder scene, and a light that is blocked adds nothing to the texel.
  * The ray, in fp32 (csrc/deferred.h: shadow_ray): origin p, tmin = 1e-3f; point and spot: dir = (pos - p) / r with
- * r = |pos - p|, tmax = (1 - 1e-3f) * r; directional: dir = -dir_l / |dir_l|, tmax = +inf; ambient lights cast none.  A ray is
+ * r = |pos - p|, tmax = (1 - 1e-3f) * r; directional: dir = -dir_l / |dir_l|, tmax = +inf; ambient lights and SH rows cast none.  A ray is
  * cast only where dir.n > 0 (for a spot also dir.s > 0), r > 0 and the record is finite; elsewhere the light counts as reaching
  * the texel.  The texel is lit iff no triangle is hit in (tmin, tmax).
  *   - A shadowed image may have at most 32 lights in its range (one bit each in the texel's visibility word): more is an error
- *     that names the image and the count.
+ *     that names the image and the count.  Bits go by row position, so SH rows count: three per SHLight.  Their bits stay set
+ *     (occluders never dim an SH row).
  *   - A scene on another device than gpu_index, `occluders` without `visibility` and a `visibility` pointer that is not 4-byte
  *     aligned are errors, raised before anything is launched.
  *   - Visibility is a CONSTANT of the adjoint: rdr_deferred_shade_backward multiplies by the saved bits -- a light whose bit is 0
  *     adds nothing to the texel's gradient nor to its own -- and produces no gradient across a shadow boundary (shadows are hard
  *     and their edges are not differentiated).
  * Both fields NULL (a zeroed tail): no shadows, the same launches and the same bits as before the fields existed. */
-enum rdr_deferred_light_type { RDR_DL_AMBIENT = 0, RDR_DL_POINT = 1, RDR_DL_DIRECTIONAL = 2, RDR_DL_SPOT = 3 };
+enum rdr_deferred_light_type { RDR_DL_AMBIENT = 0, RDR_DL_POINT = 1, RDR_DL_DIRECTIONAL = 2, RDR_DL_SPOT = 3,
+                               RDR_DL_SH_R = 4, RDR_DL_SH_G = 5, RDR_DL_SH_B = 6 };
 typedef struct rdr_deferred_desc {
     int num_images, height, width;      /* OUTPUT size */
     int aa_samples, alpha;
@@ -291,7 +306,7 @@ typedef struct rdr_deferred_desc {
     uint32_t *visibility;               /* DEV [num_images][height * aa_samples][width * aa_samples], required iff
                                            occluders != NULL (forward) / may be given alone (backward).  Bit b of a word: light
                                            range[2n] + b reaches the texel.  rdr_deferred_shade writes every word;
-                                           rdr_deferred_shade_backward reads them and needs no scene.  Bits of ambient lights and
+                                           rdr_deferred_shade_backward reads them and needs no scene.  Bits of ambient lights, of SH rows and
                                            of lights that cast no ray at the texel are 1; bits at and above the length of the
                                            image's range are 0. */
 } rdr_deferred_desc;

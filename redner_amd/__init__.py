@@ -25,7 +25,7 @@
 """
 import sys
 
-_RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'DeferredShade',
+_RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'SHLight', 'DeferredShade',
                  'deferred_shade', 'occluder_scene', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo',
                  'render_pathtracing')
 _TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid', 'envmap_sampling_tables')

@@ -143,7 +143,7 @@ class DeferredDesc(C.Structure):
 
 
 # rdr_deferred_light_type
-DL_AMBIENT, DL_POINT, DL_DIRECTIONAL, DL_SPOT = range(4)
+DL_AMBIENT, DL_POINT, DL_DIRECTIONAL, DL_SPOT, DL_SH_R, DL_SH_G, DL_SH_B = range(7)
 
 _p, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
 # Every function of the C ABI, under the header of include/ that declares it: header -> {name: (restype, argtypes)}.  load()

@@ -13,6 +13,23 @@
 //   [9] spot exponent (spot)       -- entries a type does not use are ignored and their gradient is 0.
 // Image n is lit by the lights [range[2n], range[2n+1]) of the table.
 //
+// SH ROWS (RDR_DL_SH_R / _G / _B; not in the reference, whose deferred lights are the four above): a row lights ONE colour
+// channel c with an environment given by nine spherical-harmonic coefficients, [0..8] = k_i in the order i = l*l + l + m of
+// rdr_sh_reconstruct (l = 0..2, m = -l..l); [9] is unused and its gradient is 0.  The Python SHLight is three consecutive rows.
+// The basis and the directions are those of rdr_sh_reconstruct and of an environment map with identity env_to_world: the texel
+// of the reconstructed map at (theta, phi) lies in world direction (sin phi sin theta, cos theta, -cos phi sin theta).  With the
+// texel's shading normal n AS STORED (not normalised, like the other lights), x = -n.z, y = n.x, z = n.y:
+//   Y0 =  0.28209479           Y1 = -0.48860251 y         Y2 =  0.48860251 z        Y3 = -0.48860251 x
+//   Y4 = (1.09254843 x) y      Y5 = (-1.09254843 y) z     Y6 =  0.31539157 ((3 z) z - 1)
+//   Y7 = (-1.09254843 x) z     Y8 =  0.54627422 (x x - y y)
+//   E  = sum over ascending i, from 0.f, of (A_i k_i) Y_i,   A_i = pi (l = 0), 2 pi / 3 (l = 1), pi / 4 (l = 2): the irradiance
+//   the row adds  max(E, 0) * (a_c / pi)  to channel c and nothing to the others.
+// All in fp32 in exactly that order.  The clamp (an order-2 expansion rings negative) follows the rule above: at E == 0 exactly
+// half the gradient passes, so all-zero coefficients -- where an optimisation starts -- receive a gradient.  Derivatives, for
+// the texel's upstream gradient w:  d k_i = w_c (a_c / pi) step_half(E) (A_i Y_i);  d a_c = w_c max(E, 0) / pi;  d n through
+// dY_i / d(x, y, z) and the permutation above;  d p = 0 exactly.  SH rows cast no shadow ray (like ambient rows), and their
+// bits in a visibility word stay set.
+//
 // The per-texel bodies below are shared by the kernels (one lane per OUTPUT pixel, at the end of this header) and by the plain
 // loops of the CPU debugging harness.  Arithmetic is fp32 in the order the reference's torch expressions evaluate; the only
 // fp64 is the light-parameter partial sums of the adjoint.
@@ -64,10 +81,63 @@ RDR_DEV_FN void load_texel(const float *t, Texel &x, float &alpha) {
     }
 }
 
+// ---- SH rows: the basis at a normal and the irradiance of a row, in the order the header comment states -----------------------
+constexpr int kShCoeffs = 9;
+constexpr float kShK0 = 0.282094791774f, kShK1 = 0.488602511903f, kShK2 = 1.092548430592f, kShK20 = 0.315391565253f,
+                kShK22 = 0.546274215296f;
+// the clamped-cosine factor A_i of coefficient i (a constant once the loops over i are unrolled)
+RDR_DEV_FN float sh_lobe(int i) { return i == 0 ? kPi : (i < 4 ? 2.09439510239319549f : 0.78539816339744831f); }
+RDR_DEV_FN void sh_basis(const float *n, float *Y) {
+    const float x = -n[2], y = n[0], z = n[1];
+    Y[0] = kShK0; Y[1] = -kShK1 * y; Y[2] = kShK1 * z; Y[3] = -kShK1 * x;
+    Y[4] = (kShK2 * x) * y; Y[5] = (-kShK2 * y) * z; Y[6] = kShK20 * ((3.f * z) * z - 1.f);
+    Y[7] = (-kShK2 * x) * z; Y[8] = kShK22 * (x * x - y * y);
+}
+RDR_DEV_FN float sh_irradiance(const float *k, const float *Y) {
+    float E = 0.f;
+    for (int i = 0; i < kShCoeffs; ++i) E += (sh_lobe(i) * k[i]) * Y[i];
+    return E;
+}
+// max(E, 0) of an SH row with coefficients k at a texel with normal n
+RDR_DEV_FN float sh_irradiance_at(const float *k, const float *n) {
+    float Y[kShCoeffs];
+    sh_basis(n, Y);
+    return fmaxf(sh_irradiance(k, Y), 0.f);
+}
+// The adjoint of an SH row for a (the albedo) and w (the upstream gradient) of ITS channel: da, dn += the texel's gradient; when
+// PARAMS, part[0..8] += the coefficients' instead.  The caller names the channel by a constant index (a branch per type): an
+// index computed from the type puts the kernel's per-lane arrays into scratch memory.
+template <bool PARAMS>
+RDR_DEV_FN void sh_adjoint_row(const float *k, const float *n, float a, float w, float &da, float *dn, double *part) {
+    float Y[kShCoeffs];
+    sh_basis(n, Y);
+    const float E0 = sh_irradiance(k, Y), E = fmaxf(E0, 0.f);
+    const float dE = w * (a / kPi) * step_half(E0);
+    if (PARAMS) {
+        for (int i = 0; i < kShCoeffs; ++i) part[i] += (double)(dE * (sh_lobe(i) * Y[i]));
+        return;
+    }
+    // dE / d(x, y, z) = sum_i (A_i k_i) dY_i / d(x, y, z), each sum in ascending i
+    const float x = -n[2], y = n[0], z = n[1];
+    float q[kShCoeffs];
+    for (int i = 0; i < kShCoeffs; ++i) q[i] = sh_lobe(i) * k[i];
+    const float gx = ((q[3] * -kShK1 + q[4] * (kShK2 * y)) + q[7] * (-kShK2 * z)) + q[8] * ((2.f * kShK22) * x);
+    const float gy = ((q[1] * -kShK1 + q[4] * (kShK2 * x)) + q[5] * (-kShK2 * z)) + q[8] * ((-2.f * kShK22) * y);
+    const float gz = ((q[2] * kShK1 + q[5] * (-kShK2 * y)) + q[6] * ((6.f * kShK20) * z)) + q[7] * (-kShK2 * x);
+    da += w * E / kPi;
+    dn[0] += dE * gy; dn[1] += dE * gz; dn[2] -= dE * gx;
+}
+
 // rgb += what light (type, lp) adds to texel t
 RDR_DEV_FN void light_shade(int type, const float *lp, const Texel &t, float *rgb) {
     const float *I = lp + kIntensity;
     switch (type) {
+    case RDR_DL_SH_R: case RDR_DL_SH_G: case RDR_DL_SH_B: {
+        const float E = sh_irradiance_at(lp, t.n);       // once; the three channels differ in what follows only
+        for (int k = 0; k < 3; ++k)
+            if (k == type - RDR_DL_SH_R) rgb[k] += E * (t.a[k] / kPi);
+        break;
+    }
     case RDR_DL_AMBIENT:
         for (int k = 0; k < 3; ++k) rgb[k] += I[k] * t.a[k];
         break;
@@ -108,15 +178,16 @@ RDR_DEV_FN void light_shade(int type, const float *lp, const Texel &t, float *rg
 // make_ray).  Origin p, tmin = 1e-3f and
 //   point, spot   d = pos - p, r = sqrtf(d.d):   dir = d / r,       tmax = (1 - 1e-3f) * r
 //   directional                                  dir = -D / |D|,    tmax = +inf
-//   ambient       no ray.
+//   ambient, SH   no ray.
 // A ray is cast only if dir.n > 0, for a spot also dir.s > 0, r > 0, and every float of the record is finite (tmax of a
 // directional light: +inf by the rule above, nothing else).  Background texels (normal 0) therefore never cast, and a non-finite
 // ray never reaches the traversal kernels.  A texel is lit by the light iff the any-hit query finds no triangle in (tmin, tmax);
 // a texel that casts no ray counts as lit: light_shade decides (its cosine is <= 0 or NaN there).
 constexpr float kShadowOffset = 1e-3f;
+RDR_FN bool casts_no_ray(int type) { return type == RDR_DL_AMBIENT || type >= RDR_DL_SH_R; }
 RDR_DEV_FN bool finite_f(float x) { return fabsf(x) <= 3.402823466e38f; }
 RDR_DEV_FN bool shadow_ray(int type, const float *lp, const Texel &t, rt::RayRec &rec) {
-    if (type == RDR_DL_AMBIENT) return false;
+    if (casts_no_ray(type)) return false;
     float dir[3], tmax;
     if (type == RDR_DL_DIRECTIONAL) {
         const float *D = lp + kDirection;
@@ -161,6 +232,12 @@ RDR_DEV_FN void light_adjoint(int type, const float *lp, const Texel &t, const f
             dt.a[k] += w[k] * I[k];
             if (PARAMS) part[kIntensity + k] += (double)(w[k] * t.a[k]);
         }
+        return;
+    }
+    if (type >= RDR_DL_SH_R) {
+        if (type == RDR_DL_SH_R) sh_adjoint_row<PARAMS>(lp, t.n, t.a[0], w[0], dt.a[0], dt.n, part);
+        else if (type == RDR_DL_SH_G) sh_adjoint_row<PARAMS>(lp, t.n, t.a[1], w[1], dt.a[1], dt.n, part);
+        else sh_adjoint_row<PARAMS>(lp, t.n, t.a[2], w[2], dt.a[2], dt.n, part);
         return;
     }
     float S = 0.f;           // sum_k w_k I_k a_k / pi: what multiplies the geometric factor
@@ -455,7 +532,7 @@ inline void validate(const rdr_deferred_desc &d, const char *who) {
     if (d.num_lights > 0 && !d.light_type) fail("light_type is required");
     if (!d.image_light_range) fail("image_light_range is required");
     for (int l = 0; l < d.num_lights; ++l)
-        if (d.light_type[l] < RDR_DL_AMBIENT || d.light_type[l] > RDR_DL_SPOT)
+        if (d.light_type[l] < RDR_DL_AMBIENT || d.light_type[l] > RDR_DL_SH_B)
             fail("unknown light type " + std::to_string(d.light_type[l]) + " at index " + std::to_string(l));
     for (int n = 0; n < d.num_images; ++n) {
         const int lb = d.image_light_range[2 * n], le = d.image_light_range[2 * n + 1];
@@ -554,7 +631,7 @@ inline void cast_shadows(const rdr_deferred_desc &d, const View &v, uint32_t *vi
         const Scene &scene = *reinterpret_cast<const Scene *>(d.occluders[n]);
         for (int l = lb; l < le; ++l) {
             const int type = d.light_type[l];
-            if (type == RDR_DL_AMBIENT) continue;
+            if (casts_no_ray(type)) continue;
             if (!list) {
                 list = arena.get<int>((size_t)chunk);
                 queue = arena.get<rt::RayRec>((size_t)chunk);

@@ -416,6 +416,9 @@ class DeferredLightType(enum.IntEnum):     # rdr_deferred_light_type (not in the
     point = _capi.DL_POINT
     directional = _capi.DL_DIRECTIONAL
     spot = _capi.DL_SPOT
+    sh_r = _capi.DL_SH_R               # one colour channel of a spherical-harmonic environment light (an SHLight is three rows)
+    sh_g = _capi.DL_SH_G
+    sh_b = _capi.DL_SH_B
 
 
 def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,

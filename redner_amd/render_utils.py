@@ -20,12 +20,31 @@ Per G-buffer texel with position p, normal n, albedo a, summed over the lights (
     DirectionalLight  l = -dir / |dir|:               I * max(l.n, 0) * (a / pi)
     SpotLight         l = (pos - p) / |pos - p|, s = -sdir / |sdir|:
                                                       I * pow(max(l.s, 0), e) * max(l.n, 0) * (a / pi)
+    SHLight           x = -n.z, y = n.x, z = n.y;  per colour channel c, with coeffs[c] = k:
+                      E = sum_i A_i k_i Y_i(x, y, z), A = pi, 2 pi / 3, pi / 4 for l = 0, 1, 2:
+                                                      max(E, 0) * a / pi
 
 then alpha appended unshaded and the mean over each aa x aa block.
+
+SHLight (not in the reference): an environment given by spherical-harmonic coefficients `coeffs` [3, n], n in {1, 4, 9} (rows
+r, g, b; columns in SH_reconstruct's order i = l * l + l + m; missing columns are zeros), turned into diffuse irradiance at the
+shading normal.  The basis and the directions are those of `SH_reconstruct` and of an `EnvironmentMap` with identity
+env_to_world -- the texel of the reconstructed map at (theta, phi) lies in world direction
+(sin phi sin theta, cos theta, -cos phi sin theta) -- so the same coefficients light the deferred pass and the path tracer alike:
+
+    Y0 =  0.2820948         Y1 = -0.4886025 y        Y2 =  0.4886025 z               Y3 = -0.4886025 x
+    Y4 =  1.0925484 x y     Y5 = -1.0925484 y z      Y6 =  0.3153916 (3 z z - 1)     Y7 = -1.0925484 x z
+    Y8 =  0.5462742 (x x - y y)
+
+The normal is used as stored; the position takes no part.  The clamp at 0 (an order-2 expansion rings negative) passes half the
+gradient at E == 0 exactly, so all-zero coefficients receive a gradient.  There is no rotation of the SH frame: rotate the
+coefficients or the normals.  In the light table an SHLight is three rows, one per colour channel.
 
 Shadows (`render_deferred(..., shadows=True)`, `deferred_shade(..., occluders=...)`; not in the reference): every texel casts one
 any-hit shadow ray per point, spot and directional light over the scene's triangles, on the path tracer's traversal kernels and
 with its 1e-3 offsets; a blocked light adds nothing to the texel.  Shadows are hard, and visibility is a constant of the gradient.
+Ambient lights and SHLights cast no shadow ray: occluders never dim them.  A shadowed image may have at most 32 rows in the
+light table: one per light, three per SHLight.
 """
 import random
 from typing import List, Optional, Union
@@ -104,15 +123,55 @@ class SpotLight(DeferredLight):
         return self.intensity, self.position, self.spot_direction, self.spot_exponent
 
 
+class SHLight(DeferredLight):
+    """A spherical-harmonic environment light (not in the reference): `coeffs` [3, n], n in {1, 4, 9} -- rows r, g, b, columns in
+    SH_reconstruct's order, missing columns zeros -- lights every texel by the diffuse irradiance at its shading normal (the
+    module docstring has the formula).  Three rows of the light table, one per colour channel; it casts no shadow."""
+    light_type = _default_backend.DeferredLightType.sh_r          # the first of its rows; the others follow in r, g, b order
+    num_rows = 3
+    _ROW_TYPES = tuple(int(_default_backend.DeferredLightType[n]) for n in ('sh_r', 'sh_g', 'sh_b'))
+
+    def __init__(self, coeffs: torch.Tensor):
+        self.coeffs = coeffs
+        self._checked()
+
+    def _checked(self):
+        c = torch.as_tensor(self.coeffs)
+        if c.dim() != 2 or c.shape[0] != 3 or c.shape[1] not in (1, 4, 9):
+            raise RuntimeError('SHLight: coeffs must be [3, n] with n in (1, 4, 9), got %s' % (tuple(c.shape),))
+        return c
+
+
+def _num_rows(lights):
+    """rows of the light table that a list of lights takes: one per light, three per SHLight"""
+    return sum(getattr(light, 'num_rows', 1) for light in lights)
+
+
+def _check_lights(lights):
+    """what can be refused about the lights before anything native runs"""
+    for light in lights:
+        if isinstance(light, (list, tuple)):
+            _check_lights(light)
+        elif isinstance(light, SHLight):
+            light._checked()
+
+
 def pack_lights(lights, device):
-    """[L, 10] fp32 table on `device` (layout: csrc/deferred.h) + the L light types.  One cat over the lights' tensors:
-    autograd routes the table's gradient back to them."""
+    """[L, 10] fp32 table on `device` (layout: csrc/deferred.h) + the L row types: one row per light, three (r, g, b) per
+    SHLight.  One cat over the lights' tensors: autograd routes the table's gradient back to them."""
     sizes = (3, 3, 3, 1)
     pieces, types = [], []
-    zeros = {n: torch.zeros(n, dtype=torch.float32, device=device) for n in (1, 3)}
+    zeros = {n: torch.zeros(n, dtype=torch.float32, device=device) for n in (1, 3, 6, 9)}
     for light in lights:
         if not isinstance(light, DeferredLight) or light.light_type is None:
             raise RuntimeError('render_deferred: %r is not a deferred light' % (light,))
+        if isinstance(light, SHLight):
+            coeffs = light._checked().to(device=device, dtype=torch.float32)
+            for channel, row_type in enumerate(SHLight._ROW_TYPES):       # nine coefficients (n < 9: zeros) + the unused column
+                types.append(row_type)
+                pieces.append(coeffs[channel])
+                pieces.append(zeros[_LIGHT_PARAMS - coeffs.shape[1]])
+            continue
         types.append(int(light.light_type))
         for t, n in zip(light._pieces(), sizes):
             if t is None:
@@ -228,7 +287,8 @@ def occluder_scene(scene, device: Optional[torch.device] = None, backend=None):
 def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None, occluders=None, return_visibility=False):
     """Shade a stack of G-buffers [N, H * aa, W * aa, 9 + alpha] in one launch.  `lights`: one list of DeferredLight shared by
     the N images, or N lists.  `occluders`: None (no shadows), one `occluder_scene(...)` for all images, or a list of N of them
-    (None: that image is not shadowed); a shadowed image may have at most 32 lights.  Shadows are hard and are held constant by
+    (None: that image is not shadowed); a shadowed image may have at most 32 lights, three per SHLight (they count by their rows
+    in the table, although they cast no shadow).  Shadows are hard and are held constant by
     the gradient.  `return_visibility`: also the [N, H * aa, W * aa] int32 words, bit b = light b of the image's list reaches the
     texel (all lights, when there are no occluders)."""
     n = int(g_buffer.shape[0])
@@ -236,12 +296,13 @@ def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None, oc
     if per_image:
         if len(lights) != n:
             raise RuntimeError('render_deferred: %d light lists for %d scenes' % (len(lights), n))
-        flat, ranges = [], []
-        for lgts in lights:
-            ranges.append((len(flat), len(flat) + len(lgts)))
+        flat, ranges, rows = [], [], 0
+        for lgts in lights:                  # ranges are in ROWS of the table
+            ranges.append((rows, rows + _num_rows(lgts)))
+            rows += _num_rows(lgts)
             flat.extend(lgts)
     else:
-        flat, ranges = list(lights), [(0, len(lights))] * n
+        flat, ranges = list(lights), [(0, _num_rows(lights))] * n
     params, types = pack_lights(flat, g_buffer.device)
     if occluders is None and not return_visibility:
         return DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend)
@@ -303,12 +364,13 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
     point, spot and directional light over the triangles of its scene, with the path tracer's offsets (the ray starts 1e-3 along
     its direction and, for a light with a position, ends at (1 - 1e-3) of the distance); a light that is blocked adds nothing.
     Shadows are HARD and are not differentiated across their boundary: the gradient holds visibility constant (DESIGN.md
-    section 7).  At most 32 lights per scene."""
+    section 7).  At most 32 lights per scene, three per SHLight; ambient lights and SHLights are not shadowed."""
     backend = backend or _default_backend
     device = _default_device(device)
     aa_samples = int(aa_samples)
     if aa_samples < 1:
         raise RuntimeError('render_deferred: aa_samples must be at least 1')
+    _check_lights(lights)
     channels = [backend.channels.position, backend.channels.shading_normal, backend.channels.diffuse_reflectance]
     if alpha:
         channels.append(backend.channels.alpha)
