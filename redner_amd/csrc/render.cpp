@@ -293,7 +293,7 @@ struct Backward {
     double *erd_chain = nullptr;       // [12 x chain_n] what the last finished sample left in it
     int *deferred = nullptr, *deferred_seg = nullptr, *deferred_count = nullptr, *prim_dyn = nullptr;
     int *elist[3] = {nullptr, nullptr, nullptr};
-    HLeaf *h_leaves = nullptr, *h_spill = nullptr;   // hierarchical pick: recorded leaves / spilled stack entries per list position
+    HEntry *h_leaves = nullptr, *h_spill = nullptr;   // hierarchical pick: recorded leaves / spilled stack entries per list position
     int *nee_act = nullptr;                          // lanes of a depth whose next-event estimate has something to differentiate
     HDescent *h_descent = nullptr;                   // ... and what the descent hands to the leaf launch (stages_edge.h)
     GatherShared gshared{nullptr, nullptr, nullptr, nullptr, 0, 0};     // heavy slots of the gather: big candidate lists, subtree work items
@@ -389,8 +389,8 @@ struct Backward {
             // tests: small lists, so that the overflow paths run (rdr_tuning::gather_*_cap_plus1)
             if (tuning().gather_heavy_cap >= 0) gshared.heavy_cap = std::min(tuning().gather_heavy_cap, gshared.heavy_cap);
             if (tuning().gather_work_cap >= 0) gshared.work_cap = std::min(tuning().gather_work_cap, gshared.work_cap);
-            h_leaves = arena.get<HLeaf>((size_t)kHSamples * P);
-            h_spill = arena.get<HLeaf>((size_t)(kHSamples - kHStackLds) * P);
+            h_leaves = arena.get<HEntry>((size_t)kHSamples * P);
+            h_spill = arena.get<HEntry>((size_t)(kHSamples - kHStackLds) * P);
             h_descent = arena.get<HDescent>((size_t)P);
             edge_contrib = arena.get<double>(L);
             edge_tmin = arena.get<double>(L);

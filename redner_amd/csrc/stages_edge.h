@@ -475,22 +475,51 @@ constexpr int kHStack = 16;
 // few stack sizes and the host picks the smallest that covers the scene's trees (EdgeSceneD::max_stack).
 constexpr int kNStackMax = 64;
 
-struct HItem { int ref, num; double pmf; };
+// One entry of the hierarchical pick, 16 B: on the descent's stack (and in its spill buffer) `ref` is a node reference or, for
+// a leaf, ~edge id; in the list of recorded leaves it is ~edge id.  `num` of the kHSamples samples, reached with probability `pmf`.
+struct HEntry { int ref, num; double pmf; };
 
-// Stochastic top-down pick of one edge, splitting kHSamples "samples" by LTC-bounded importance
-// and keeping one leaf by reservoir sampling.  Returns the edge id or -1; weight = 1/pmf.
-RDR_DEV_FN int pick_edge_hierarchical(const SceneD &sc, const EdgeSceneD &es, const LtcCtx &c,
-                                      double sample, double resample, double &weight) {
-    const SilQuery q_pos = sil_query(es, c.pos);
-    RDR_STACK_DECL(int, st_ref, kHStack);
-    RDR_STACK_DECL(unsigned char, st_num, kHStack);
-    RDR_STACK_DECL(double, st_pmf, kHStack);
-#define RDR_H_PUSH(r, n, p) { RDR_STACK_AT(st_ref, sp) = (r); RDR_STACK_AT(st_num, sp) = (unsigned char)(n); RDR_STACK_AT(st_pmf, sp) = (p); sp++; }
-    int sp = 0;
-    int selected = -1;
-    double edge_w = 0, wsum = 0;
+// ---- the rules of the picks, each stated once ------------------------------------------------------------------------------
+// One random number goes through ~100 of these rescalings per pick and one different last bit draws another edge,
+// so every kernel form below calls these: fp64 throughout, no contraction, the reference's operation order, and nothing
+// hoisted across the `prev == 0` test.  What a form keeps to itself is where its stack lives, whether leaves are evaluated
+// in place or recorded, and whether it is a loop or a walk.
+
+// Reservoir update over one candidate of weight `w` (src/edge.cpp:1300-1316): true = the candidate replaces the selection.
+// `resample` is rescaled to [0, 1) again in both branches.
+RDR_FN bool reservoir_step(double w, double &wsum, double &resample) {
+    double prev = wsum;
+    wsum += w;
+    double nw = w / wsum;
+    if (resample <= nw || prev == 0) {
+        resample /= nw;
+        return true;
+    }
+    resample = (resample - nw) / (1 - nw);
+    return false;
+}
+// A leaf of the hierarchical pick: its samples times its importance over the probability of reaching it.
+RDR_FN void h_leaf_step(const SceneD &sc, const EdgeSceneD &es, const LtcCtx &c, const HEntry &it,
+                        int &selected, double &edge_w, double &wsum, double &resample) {
+    const int leaf_edge = ~it.ref;
+    double w = it.num * leaf_importance_h(sc, es, leaf_edge, c) / it.pmf;
+    if (w > 0 && reservoir_step(w, wsum, resample)) {
+        selected = leaf_edge;
+        edge_w = w * it.pmf;
+    }
+}
+// Result of the hierarchical pick: the edge id or -1; weight = 1 / pmf.
+RDR_FN int h_pick_result(int selected, double edge_w, double wsum, double &weight) {
+    if (edge_w <= 0 || wsum <= 0) return -1;
+    double pmf_h = edge_w * kHSamples / wsum;
+    weight = 1 / pmf_h;
+    return selected;
+}
+// The kHSamples samples split between the two trees; push(ref, num, pmf) takes each root that got some.  False: no edge tree.
+template <class Push>
+RDR_DEV_FN bool h_root_split(const EdgeSceneD &es, double &sample, const Push &push) {
     double imp_cs = es.cs_root != kNoEdgeTree ? 1.0 : 0.0, imp_ncs = es.ncs_root != kNoEdgeTree ? 1.0 : 0.0;
-    if (imp_cs <= 0 && imp_ncs <= 0) return -1;
+    if (imp_cs <= 0 && imp_ncs <= 0) return false;
     double prob_cs = imp_cs / (imp_cs + imp_ncs), prob_ncs = 1 - prob_cs;
     double exp_cs = kHSamples * prob_cs, exp_ncs = kHSamples * prob_ncs;
     int n_cs = int(floor(exp_cs)), n_ncs = int(floor(exp_ncs));
@@ -499,64 +528,10 @@ RDR_DEV_FN int pick_edge_hierarchical(const SceneD &sc, const EdgeSceneD &es, co
         if (sample < prob) { n_cs++; sample /= prob; }
         else { n_ncs++; sample = (sample - prob) / (1 - prob); }
     }
-    if (n_cs > 0) RDR_H_PUSH(es.cs_root, n_cs, prob_cs)
-    if (n_ncs > 0) RDR_H_PUSH(es.ncs_root, n_ncs, prob_ncs)
-    while (sp > 0) {
-        --sp;
-        HItem it = HItem{RDR_STACK_AT(st_ref, sp), (int)RDR_STACK_AT(st_num, sp), RDR_STACK_AT(st_pmf, sp)};
-        if (it.ref < 0) {
-            const int leaf_edge = ~it.ref;
-            double w = it.num * leaf_importance_h(sc, es, leaf_edge, c) / it.pmf;
-            if (w > 0) {
-                double prev = wsum;
-                wsum += w;
-                double nw = w / wsum;
-                if (resample <= nw || prev == 0) {
-                    selected = leaf_edge;
-                    edge_w = w * it.pmf;
-                    resample /= nw;
-                } else {
-                    resample = (resample - nw) / (1 - nw);
-                }
-            }
-        } else {
-            const EdgeNodeP &nd = edge_node(es, it.ref);
-            const int tree = it.ref & kEdgeTreeBit;
-            const bool tree3d = tree == 0;
-            int c0 = nd.c_ref[0] < 0 ? nd.c_ref[0] : (nd.c_ref[0] | tree);
-            int c1 = nd.c_ref[1] < 0 ? nd.c_ref[1] : (nd.c_ref[1] | tree);
-            double i0, i1;
-            if (box_contains(v3_of(nd.p_min), v3_of(nd.p_max), c.pos)) { i0 = i1 = 1; }
-            else { i0 = node_importance(nd, 0, tree3d, c, q_pos); i1 = node_importance(nd, 1, tree3d, c, q_pos); }
-            if (i0 > 0 || i1 > 0) {
-                double p0 = i0 / (i0 + i1), p1 = 1 - p0;
-                double e0 = it.num * p0, e1 = it.num * p1;
-                int s0 = int(floor(e0)), s1 = int(floor(e1));
-                if (s0 + s1 < it.num) {
-                    double prob = e0 - s0;
-                    if (sample < prob) { s0++; sample /= prob; }
-                    else { s1++; sample = (sample - prob) / (1 - prob); }
-                }
-                if (s0 > 0 && sp < kHStack) RDR_H_PUSH(c0, s0, it.pmf * p0)
-                if (s1 > 0 && sp < kHStack) RDR_H_PUSH(c1, s1, it.pmf * p1)
-            }
-        }
-    }
-    if (edge_w <= 0 || wsum <= 0) return -1;
-    double pmf_h = edge_w * kHSamples / wsum;
-    weight = 1 / pmf_h;
-    return selected;
-#undef RDR_H_PUSH
+    if (n_cs > 0) push(es.cs_root, n_cs, prob_cs);
+    if (n_ncs > 0) push(es.ncs_root, n_ncs, prob_ncs);
+    return true;
 }
-
-// The same pick with the leaf work deferred (SecEdgePickH2).  Interior steps consume only `sample`, leaf steps only
-// `resample` and the reservoir, so the two sequences are independent: the descent records the leaves it pops, in pop
-// order, and a second loop evaluates their importance and runs the reservoir -- the same operations on the same operands
-// in the same order per variable.  On the GPU the lanes of a wave then run the (cheap, uniform) descent together and the
-// (expensive: silhouette test + two LTC line integrals) leaf evaluations together instead of serialising the two bodies
-// whenever a wave holds both kinds of entries (lane utilisation of the fused loop: 0.44, profiles/r1_pmc_sq.csv).
-// The descent stack keeps kHStackLds entries per lane in LDS (13 B each: 4 workgroups per CU instead of 3) and spills the
-// rare deeper entries to `spill`; the leaf list lives in HBM (written and read once, coalesced by entry index).
 // One interior node = one 128-byte line.  Left to itself the compiler sinks each field's load into the branch that first
 // uses it (the tests have early outs), which turns a step into ~9 dependent L1 round trips; this fetches the line with
 // eight 16-byte loads issued together and pins them in registers.
@@ -574,11 +549,72 @@ RDR_DEV_FN EdgeNodeP load_node_line(const EdgeNodeP *p) {
     return *p;
 #endif
 }
-struct HLeaf { int ref, num; double pmf; };        // 16 B; ref: ~edge id for leaves, node reference for spilled stack entries
+// The samples of a popped interior node split between its children by LTC-bounded importance; push(ref, num, pmf) takes
+// each child that got some while fits() says the form's stack has room for another entry.  PRELOAD: load_node_line.
+template <bool PRELOAD, class Fits, class Push>
+RDR_DEV_FN void h_node_split(const EdgeSceneD &es, const LtcCtx &c, const SilQuery &q_pos, const HEntry &it, double &sample,
+                             const Fits &fits, const Push &push) {
+    const EdgeNodeP nd_line = PRELOAD ? load_node_line(&edge_node(es, it.ref)) : EdgeNodeP();
+    const EdgeNodeP &nd = PRELOAD ? nd_line : edge_node(es, it.ref);
+    const int tree = it.ref & kEdgeTreeBit;
+    const bool tree3d = tree == 0;
+    int c0 = nd.c_ref[0] < 0 ? nd.c_ref[0] : (nd.c_ref[0] | tree);
+    int c1 = nd.c_ref[1] < 0 ? nd.c_ref[1] : (nd.c_ref[1] | tree);
+    double i0, i1;
+    if (box_contains(v3_of(nd.p_min), v3_of(nd.p_max), c.pos)) { i0 = i1 = 1; }
+    else { i0 = node_importance(nd, 0, tree3d, c, q_pos); i1 = node_importance(nd, 1, tree3d, c, q_pos); }
+    if (i0 > 0 || i1 > 0) {
+        double p0 = i0 / (i0 + i1), p1 = 1 - p0;
+        double e0 = it.num * p0, e1 = it.num * p1;
+        int s0 = int(floor(e0)), s1 = int(floor(e1));
+        if (s0 + s1 < it.num) {
+            double prob = e0 - s0;
+            if (sample < prob) { s0++; sample /= prob; }
+            else { s1++; sample = (sample - prob) / (1 - prob); }
+        }
+        if (s0 > 0 && fits()) push(c0, s0, it.pmf * p0);
+        if (s1 > 0 && fits()) push(c1, s1, it.pmf * p1);
+    }
+}
+
+// Stochastic top-down pick of one edge, splitting kHSamples "samples" by LTC-bounded importance
+// and keeping one leaf by reservoir sampling.  Returns the edge id or -1; weight = 1/pmf.
+RDR_DEV_FN int pick_edge_hierarchical(const SceneD &sc, const EdgeSceneD &es, const LtcCtx &c,
+                                      double sample, double resample, double &weight) {
+    const SilQuery q_pos = sil_query(es, c.pos);
+    RDR_STACK_DECL(int, st_ref, kHStack);
+    RDR_STACK_DECL(unsigned char, st_num, kHStack);
+    RDR_STACK_DECL(double, st_pmf, kHStack);
+    int sp = 0;
+    auto push = [&](int r, int n, double p) {
+        RDR_STACK_AT(st_ref, sp) = r; RDR_STACK_AT(st_num, sp) = (unsigned char)n; RDR_STACK_AT(st_pmf, sp) = p;
+        sp++;
+    };
+    int selected = -1;
+    double edge_w = 0, wsum = 0;
+    if (!h_root_split(es, sample, push)) return -1;
+    while (sp > 0) {
+        --sp;
+        const HEntry it = HEntry{RDR_STACK_AT(st_ref, sp), (int)RDR_STACK_AT(st_num, sp), RDR_STACK_AT(st_pmf, sp)};
+        if (it.ref < 0) h_leaf_step(sc, es, c, it, selected, edge_w, wsum, resample);
+        else h_node_split<false>(es, c, q_pos, it, sample, [&] { return sp < kHStack; }, push);
+    }
+    return h_pick_result(selected, edge_w, wsum, weight);
+}
+
+// The same pick with the leaf work deferred (SecEdgePickH2).  Interior steps consume only `sample`, leaf steps only
+// `resample` and the reservoir, so the two sequences are independent: the descent records the leaves it pops, in pop
+// order, and a second loop evaluates their importance and runs the reservoir -- the same operations on the same operands
+// in the same order per variable.  On the GPU the lanes of a wave then run the (cheap, uniform) descent together and the
+// (expensive: silhouette test + two LTC line integrals) leaf evaluations together instead of serialising the two bodies
+// whenever a wave holds both kinds of entries (lane utilisation of the fused loop: 0.44, profiles/r1_pmc_sq.csv).
+// The descent stack keeps kHStackLds entries per lane in LDS (13 B each: 4 workgroups per CU instead of 3) and spills the
+// rare deeper entries to `spill`; the leaf list lives in HBM (written and read once, coalesced by entry index).
+// (The interior node's line is fetched by load_node_line when PRELOAD is set.)
 constexpr int kHStackLds = 12;
 template <bool PRELOAD>
 RDR_DEV_FN int pick_edge_hierarchical_deferred(const SceneD &sc, const EdgeSceneD &es, const LtcCtx &c, double sample, double resample,
-                                               double &weight, HLeaf *leaves, HLeaf *spill, size_t stride) {
+                                               double &weight, HEntry *leaves, HEntry *spill, size_t stride) {
     const SilQuery q_pos = sil_query(es, c.pos);
     RDR_STACK_DECL(int, st_ref, kHStackLds);
     RDR_STACK_DECL(unsigned char, st_num, kHStackLds);
@@ -586,77 +622,27 @@ RDR_DEV_FN int pick_edge_hierarchical_deferred(const SceneD &sc, const EdgeScene
     int sp = 0, nleaf = 0;
     auto push = [&](int r, int n, double p) {
         if (sp < kHStackLds) { RDR_STACK_AT(st_ref, sp) = r; RDR_STACK_AT(st_num, sp) = (unsigned char)n; RDR_STACK_AT(st_pmf, sp) = p; }
-        else spill[(size_t)(sp - kHStackLds) * stride] = HLeaf{r, n, p};
+        else spill[(size_t)(sp - kHStackLds) * stride] = HEntry{r, n, p};
         sp++;
     };
-    double imp_cs = es.cs_root != kNoEdgeTree ? 1.0 : 0.0, imp_ncs = es.ncs_root != kNoEdgeTree ? 1.0 : 0.0;
-    if (imp_cs <= 0 && imp_ncs <= 0) return -1;
-    double prob_cs = imp_cs / (imp_cs + imp_ncs), prob_ncs = 1 - prob_cs;
-    double exp_cs = kHSamples * prob_cs, exp_ncs = kHSamples * prob_ncs;
-    int n_cs = int(floor(exp_cs)), n_ncs = int(floor(exp_ncs));
-    if (n_cs + n_ncs < kHSamples) {
-        double prob = exp_cs - n_cs;
-        if (sample < prob) { n_cs++; sample /= prob; }
-        else { n_ncs++; sample = (sample - prob) / (1 - prob); }
-    }
-    if (n_cs > 0) push(es.cs_root, n_cs, prob_cs);
-    if (n_ncs > 0) push(es.ncs_root, n_ncs, prob_ncs);
+    if (!h_root_split(es, sample, push)) return -1;
     // every live entry (pending or recorded leaf) carries >= 1 of the kHSamples samples: sp + nleaf <= kHSamples
     while (sp > 0) {
         --sp;
-        HItem it;
-        if (sp < kHStackLds) it = HItem{RDR_STACK_AT(st_ref, sp), (int)RDR_STACK_AT(st_num, sp), RDR_STACK_AT(st_pmf, sp)};
-        else { const HLeaf sl = spill[(size_t)(sp - kHStackLds) * stride]; it = HItem{sl.ref, sl.num, sl.pmf}; }
+        HEntry it;
+        if (sp < kHStackLds) it = HEntry{RDR_STACK_AT(st_ref, sp), (int)RDR_STACK_AT(st_num, sp), RDR_STACK_AT(st_pmf, sp)};
+        else it = spill[(size_t)(sp - kHStackLds) * stride];
         if (it.ref < 0) {
-            leaves[(size_t)nleaf * stride] = HLeaf{it.ref, it.num, it.pmf};
+            leaves[(size_t)nleaf * stride] = it;
             nleaf++;
             continue;
         }
-        const EdgeNodeP nd_line = PRELOAD ? load_node_line(&edge_node(es, it.ref)) : EdgeNodeP();
-        const EdgeNodeP &nd = PRELOAD ? nd_line : edge_node(es, it.ref);
-        const int tree = it.ref & kEdgeTreeBit;
-        const bool tree3d = tree == 0;
-        int c0 = nd.c_ref[0] < 0 ? nd.c_ref[0] : (nd.c_ref[0] | tree);
-        int c1 = nd.c_ref[1] < 0 ? nd.c_ref[1] : (nd.c_ref[1] | tree);
-        double i0, i1;
-        if (box_contains(v3_of(nd.p_min), v3_of(nd.p_max), c.pos)) { i0 = i1 = 1; }
-        else { i0 = node_importance(nd, 0, tree3d, c, q_pos); i1 = node_importance(nd, 1, tree3d, c, q_pos); }
-        if (i0 > 0 || i1 > 0) {
-            double p0 = i0 / (i0 + i1), p1 = 1 - p0;
-            double e0 = it.num * p0, e1 = it.num * p1;
-            int s0 = int(floor(e0)), s1 = int(floor(e1));
-            if (s0 + s1 < it.num) {
-                double prob = e0 - s0;
-                if (sample < prob) { s0++; sample /= prob; }
-                else { s1++; sample = (sample - prob) / (1 - prob); }
-            }
-            if (s0 > 0 && sp + nleaf < kHSamples) push(c0, s0, it.pmf * p0);
-            if (s1 > 0 && sp + nleaf < kHSamples) push(c1, s1, it.pmf * p1);
-        }
+        h_node_split<PRELOAD>(es, c, q_pos, it, sample, [&] { return sp + nleaf < kHSamples; }, push);
     }
     int selected = -1;
     double edge_w = 0, wsum = 0;
-    for (int j = 0; j < nleaf; ++j) {
-        const HLeaf it = leaves[(size_t)j * stride];
-        const int leaf_edge = ~it.ref;
-        double w = it.num * leaf_importance_h(sc, es, leaf_edge, c) / it.pmf;
-        if (w > 0) {
-            double prev = wsum;
-            wsum += w;
-            double nw = w / wsum;
-            if (resample <= nw || prev == 0) {
-                selected = leaf_edge;
-                edge_w = w * it.pmf;
-                resample /= nw;
-            } else {
-                resample = (resample - nw) / (1 - nw);
-            }
-        }
-    }
-    if (edge_w <= 0 || wsum <= 0) return -1;
-    double pmf_h = edge_w * kHSamples / wsum;
-    weight = 1 / pmf_h;
-    return selected;
+    for (int j = 0; j < nleaf; ++j) h_leaf_step(sc, es, c, leaves[(size_t)j * stride], selected, edge_w, wsum, resample);
+    return h_pick_result(selected, edge_w, wsum, weight);
 }
 
 // Tail of the NEE-mode pick: pmf of the selected edge, Jacobian of the NEE-ray / billboard intersection, point on the edge.
@@ -785,6 +771,19 @@ struct SecEdgeArgs {          // what every stage of the sampler needs
     SamplerD rng_edge; int dim_edge;      // edge sampler: 4 numbers per compacted slot
     const int *active; VSlice v;        // main-path vertex
 };
+// Tail of the NEE-mode pick, after the reservoir chose `selected` (-1: none): weight, point on the edge and edge vector
+// (src/edge.cpp:1319-1363); the NEE segment is rebuilt from the slot rather than carried through the walk or the gather.
+RDR_FN SecPick nee_pick_tail(const SecEdgeArgs &a, int idx, int selected, double edge_w, double wsum) {
+    SecPick out{-1, 0.0, v3(0), v3(0)};
+    if (selected != -1) {
+        SecPre s = sec_prepare(a.sc, a.es, a.rng_main, a.dim_main, a.rng_edge, a.dim_edge, a.v, a.active[idx], idx);
+        double ew = 0;
+        V3 sample_p = v3(0), mwt = v3(0);
+        int eid = finish_edge_nee(a.sc, a.es, s.nee, s.nee_valid, s.nee_pt, s.nee_shape, selected, edge_w, wsum, ew, sample_p, mwt);
+        out = SecPick{eid, ew, sample_p, mwt};
+    }
+    return out;
+}
 
 // mode[slot]: 0 = no sample, 1 = hierarchical pick, 2 / 3 = NEE-billboard pick (3: the vertex lies on a shape with at least
 // kDenseShapeTriangles triangles).  Also resets the slot's outputs.
@@ -792,6 +791,13 @@ constexpr int kDenseShapeTriangles = 512;
 // What the slot set-up hands to the hierarchical pick (SecEdgePickHDescend / SecEdgePickHLeaves below): shading position, LTC
 // matrix and the two random numbers of the pick -- sec_prepare's results, computed once here instead of again in the pick.
 struct HDescent { double pos[3], m_inv[9], sample, resample; int nleaf, pad; };      // 120 B per slot
+// The record's LTC context: pos and m_inv.  m is left zero -- the leaves need only m_inv; the descent forms the inverse itself.
+RDR_FN LtcCtx ltc_of(const HDescent &d) {
+    LtcCtx c;
+    c.pos = V3{d.pos[0], d.pos[1], d.pos[2]};
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) { c.m_inv.m[r][k] = d.m_inv[3 * r + k]; c.m.m[r][k] = 0; }
+    return c;
+}
 struct SecEdgeSetup {
     SecEdgeArgs a; unsigned char *mode; SecondaryEdgeRec *recs; SecPick *picks; VSlice ev; double *edge_tmin;
     HDescent *hd = nullptr;         // null: the one-launch forms of the pick (they call sec_prepare themselves)
@@ -847,7 +853,7 @@ struct SecEdgePickH {
     }
 };
 template <bool PRELOAD> struct SecEdgePickH2 {        // the hierarchical pick with deferred leaf evaluation (pick_edge_hierarchical_deferred)
-    SecEdgeArgs a; const int *slots; SecPick *picks; HLeaf *leaves, *spill; int n;      // leaves: kHSamples x n, spill: (kHSamples - kHStackLds) x n
+    SecEdgeArgs a; const int *slots; SecPick *picks; HEntry *leaves, *spill; int n;      // leaves: kHSamples x n, spill: (kHSamples - kHStackLds) x n
     RDR_FN void make_lean() { lean_scene(a.sc); lean_slice(a.v); }
     RDR_FN void make_mid() { mid_scene(a.sc); }
     RDR_FN void operator()(int i) const {
@@ -870,7 +876,7 @@ template <bool PRELOAD> struct SecEdgePickH2 {        // the hierarchical pick w
 //   SecEdgePickHLeaves   one lane per slot: importance of the recorded leaves in pop order, reservoir, SecPick.
 // Same operations on the same operands in the same order per slot as pick_edge_hierarchical_deferred: identical picks.
 template <bool PRELOAD> struct SecEdgePickHDescend {
-    EdgeSceneD es; const int *slots; HLeaf *leaves, *spill; HDescent *hd; int n;
+    EdgeSceneD es; const int *slots; HEntry *leaves, *spill; HDescent *hd; int n;
     struct State {
         int i, idx, sp, nleaf;
         double sample;
@@ -887,29 +893,18 @@ template <bool PRELOAD> struct SecEdgePickHDescend {
         auto st_num = RDR_WALK_STACK(st, unsigned char, st_num, kHStackLds, 12);
         auto st_pmf = RDR_WALK_STACK(st, double, st_pmf, kHStackLds, 13);
         if (st.sp < kHStackLds) { RDR_WALK_AT(st_ref, st.sp) = r; RDR_WALK_AT(st_num, st.sp) = (unsigned char)nn; RDR_WALK_AT(st_pmf, st.sp) = p; }
-        else spill[(size_t)(st.sp - kHStackLds) * (size_t)n + st.i] = HLeaf{r, nn, p};
+        else spill[(size_t)(st.sp - kHStackLds) * (size_t)n + st.i] = HEntry{r, nn, p};
         st.sp++;
     }
     RDR_DEV_FN bool begin(int i, State &st) const {
         st.i = i; st.idx = slots[i]; st.sp = 0; st.nleaf = 0;
         const HDescent d = hd[st.idx];
         st.sample = d.sample;
-        st.c.pos = V3{d.pos[0], d.pos[1], d.pos[2]};
-        for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) st.c.m_inv.m[r][k] = d.m_inv[3 * r + k];
+        st.c = ltc_of(d);
         st.c.m = m3_inverse(st.c.m_inv);              // as sec_prepare does (ltc_bound needs both; the leaves only m_inv)
         st.q_pos = sil_query(es, st.c.pos);
-        double imp_cs = es.cs_root != kNoEdgeTree ? 1.0 : 0.0, imp_ncs = es.ncs_root != kNoEdgeTree ? 1.0 : 0.0;
-        if (imp_cs <= 0 && imp_ncs <= 0) { st.nleaf = -1; return false; }            // no edge tree: the pick returns -1
-        double prob_cs = imp_cs / (imp_cs + imp_ncs), prob_ncs = 1 - prob_cs;
-        double exp_cs = kHSamples * prob_cs, exp_ncs = kHSamples * prob_ncs;
-        int n_cs = int(floor(exp_cs)), n_ncs = int(floor(exp_ncs));
-        if (n_cs + n_ncs < kHSamples) {
-            double prob = exp_cs - n_cs;
-            if (st.sample < prob) { n_cs++; st.sample /= prob; }
-            else { n_ncs++; st.sample = (st.sample - prob) / (1 - prob); }
-        }
-        if (n_cs > 0) push(st, es.cs_root, n_cs, prob_cs);
-        if (n_ncs > 0) push(st, es.ncs_root, n_ncs, prob_ncs);
+        const bool trees = h_root_split(es, st.sample, [&](int r, int nn, double p) { push(st, r, nn, p); });
+        if (!trees) { st.nleaf = -1; return false; }            // no edge tree: the pick returns -1
         return st.sp > 0;
     }
     RDR_DEV_FN bool step(State &st) const {
@@ -917,78 +912,41 @@ template <bool PRELOAD> struct SecEdgePickHDescend {
         auto st_num = RDR_WALK_STACK(st, unsigned char, st_num, kHStackLds, 12);
         auto st_pmf = RDR_WALK_STACK(st, double, st_pmf, kHStackLds, 13);
         --st.sp;
-        HItem it;
-        if (st.sp < kHStackLds) it = HItem{RDR_WALK_AT(st_ref, st.sp), (int)RDR_WALK_AT(st_num, st.sp), RDR_WALK_AT(st_pmf, st.sp)};
-        else { const HLeaf sl = spill[(size_t)(st.sp - kHStackLds) * (size_t)n + st.i]; it = HItem{sl.ref, sl.num, sl.pmf}; }
+        HEntry it;
+        if (st.sp < kHStackLds) it = HEntry{RDR_WALK_AT(st_ref, st.sp), (int)RDR_WALK_AT(st_num, st.sp), RDR_WALK_AT(st_pmf, st.sp)};
+        else it = spill[(size_t)(st.sp - kHStackLds) * (size_t)n + st.i];
         if (it.ref < 0) {
-            leaves[(size_t)st.nleaf * (size_t)n + st.i] = HLeaf{it.ref, it.num, it.pmf};
+            leaves[(size_t)st.nleaf * (size_t)n + st.i] = it;
             st.nleaf++;
             return st.sp == 0;
         }
-        const EdgeNodeP nd_line = PRELOAD ? load_node_line(&edge_node(es, it.ref)) : EdgeNodeP();
-        const EdgeNodeP &nd = PRELOAD ? nd_line : edge_node(es, it.ref);
-        const int tree = it.ref & kEdgeTreeBit;
-        const bool tree3d = tree == 0;
-        int c0 = nd.c_ref[0] < 0 ? nd.c_ref[0] : (nd.c_ref[0] | tree);
-        int c1 = nd.c_ref[1] < 0 ? nd.c_ref[1] : (nd.c_ref[1] | tree);
-        double i0, i1;
-        if (box_contains(v3_of(nd.p_min), v3_of(nd.p_max), st.c.pos)) { i0 = i1 = 1; }
-        else { i0 = node_importance(nd, 0, tree3d, st.c, st.q_pos); i1 = node_importance(nd, 1, tree3d, st.c, st.q_pos); }
-        if (i0 > 0 || i1 > 0) {
-            double p0 = i0 / (i0 + i1), p1 = 1 - p0;
-            double e0 = it.num * p0, e1 = it.num * p1;
-            int s0 = int(floor(e0)), s1 = int(floor(e1));
-            if (s0 + s1 < it.num) {
-                double prob = e0 - s0;
-                if (st.sample < prob) { s0++; st.sample /= prob; }
-                else { s1++; st.sample = (st.sample - prob) / (1 - prob); }
-            }
-            if (s0 > 0 && st.sp + st.nleaf < kHSamples) push(st, c0, s0, it.pmf * p0);
-            if (s1 > 0 && st.sp + st.nleaf < kHSamples) push(st, c1, s1, it.pmf * p1);
-        }
+        h_node_split<PRELOAD>(es, st.c, st.q_pos, it, st.sample, [&] { return st.sp + st.nleaf < kHSamples; },
+                              [&](int r, int nn, double p) { push(st, r, nn, p); });
         return st.sp == 0;
     }
     RDR_DEV_FN void finish(State &st) const { hd[st.idx].nleaf = st.nleaf; }
 };
 struct SecEdgePickHLeaves {
-    SecEdgeArgs a; const int *slots; SecPick *picks; const HLeaf *leaves; const HDescent *in; int n;
+    SecEdgeArgs a; const int *slots; SecPick *picks; const HEntry *leaves; const HDescent *in; int n;
     RDR_FN void make_lean() { lean_scene(a.sc); lean_slice(a.v); }
     RDR_FN void make_mid() { mid_scene(a.sc); }
     RDR_FN void operator()(int i) const {
         const int idx = slots[i];
         const HDescent d = in[idx];
-        LtcCtx c;
-        c.pos = V3{d.pos[0], d.pos[1], d.pos[2]};
-        for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) { c.m_inv.m[r][k] = d.m_inv[3 * r + k]; c.m.m[r][k] = 0; }
+        const LtcCtx c = ltc_of(d);
         double resample = d.resample;
         int selected = -1;
         double edge_w = 0, wsum = 0;
-        for (int j = 0; j < d.nleaf; ++j) {
-            const HLeaf it = leaves[(size_t)j * (size_t)n + i];
-            const int leaf_edge = ~it.ref;
-            double w = it.num * leaf_importance_h(a.sc, a.es, leaf_edge, c) / it.pmf;
-            if (w > 0) {
-                double prev = wsum;
-                wsum += w;
-                double nw = w / wsum;
-                if (resample <= nw || prev == 0) {
-                    selected = leaf_edge;
-                    edge_w = w * it.pmf;
-                    resample /= nw;
-                } else {
-                    resample = (resample - nw) / (1 - nw);
-                }
-            }
-        }
+        for (int j = 0; j < d.nleaf; ++j) h_leaf_step(a.sc, a.es, c, leaves[(size_t)j * (size_t)n + i], selected, edge_w, wsum, resample);
         int eid = -1;
         double ew = 0;
-        if (d.nleaf >= 0 && !(edge_w <= 0 || wsum <= 0)) { ew = 1 / (edge_w * kHSamples / wsum); eid = selected; }
+        if (d.nleaf >= 0) eid = h_pick_result(selected, edge_w, wsum, ew);
         picks[idx] = SecPick{eid, ew, v3(0), v3(0)};
     }
 };
 // SecEdgePickHLeaves as a walk (one recorded leaf per step) for exec::launch_chunked: slots record 1 ... 16 leaves.
 struct SecEdgePickHLeavesWalk {
-    SceneD sc; EdgeSceneD es; const int *slots; SecPick *picks; const HLeaf *leaves; const HDescent *in; int n;
+    SceneD sc; EdgeSceneD es; const int *slots; SecPick *picks; const HEntry *leaves; const HDescent *in; int n;
     struct State { int i, idx, j, nleaf, selected; double resample, edge_w, wsum; LtcCtx c; };
     RDR_FN void make_lean() { lean_scene(sc); }
     RDR_FN void make_mid() { mid_scene(sc); }
@@ -996,32 +954,17 @@ struct SecEdgePickHLeavesWalk {
         st.i = i; st.idx = slots[i]; st.j = 0; st.selected = -1; st.edge_w = 0; st.wsum = 0;
         const HDescent d = in[st.idx];
         st.nleaf = d.nleaf; st.resample = d.resample;
-        st.c.pos = V3{d.pos[0], d.pos[1], d.pos[2]};
-        for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) { st.c.m_inv.m[r][k] = d.m_inv[3 * r + k]; st.c.m.m[r][k] = 0; }
+        st.c = ltc_of(d);
         return st.nleaf > 0;
     }
     RDR_DEV_FN bool step(State &st) const {
-        const HLeaf it = leaves[(size_t)st.j * (size_t)n + st.i];
-        const int leaf_edge = ~it.ref;
-        double w = it.num * leaf_importance_h(sc, es, leaf_edge, st.c) / it.pmf;
-        if (w > 0) {
-            double prev = st.wsum;
-            st.wsum += w;
-            double nw = w / st.wsum;
-            if (st.resample <= nw || prev == 0) {
-                st.selected = leaf_edge;
-                st.edge_w = w * it.pmf;
-                st.resample /= nw;
-            } else {
-                st.resample = (st.resample - nw) / (1 - nw);
-            }
-        }
+        h_leaf_step(sc, es, st.c, leaves[(size_t)st.j * (size_t)n + st.i], st.selected, st.edge_w, st.wsum, st.resample);
         return ++st.j >= st.nleaf;
     }
     RDR_DEV_FN void finish(State &st) const {
         int eid = -1;
         double ew = 0;
-        if (st.nleaf >= 0 && !(st.edge_w <= 0 || st.wsum <= 0)) { ew = 1 / (st.edge_w * kHSamples / st.wsum); eid = st.selected; }
+        if (st.nleaf >= 0) eid = h_pick_result(st.selected, st.edge_w, st.wsum, ew);
         picks[st.idx] = SecPick{eid, ew, v3(0), v3(0)};
     }
 };
@@ -1065,13 +1008,7 @@ template <int NS> struct SecEdgePickNWalk {
         if (ref < 0) {
             const int leaf_edge = ~ref;
             double w = leaf_importance_l(sc, es, leaf_edge, st.c, st.nee, st.nee_valid);
-            if (w > 0) {
-                double prev = st.wsum;
-                st.wsum += w;
-                double nw = w / st.wsum;
-                if (st.resample <= nw || prev == 0) { st.selected = leaf_edge; st.edge_w = w; st.resample /= nw; }
-                else st.resample = (st.resample - nw) / (1 - nw);
-            }
+            if (w > 0 && reservoir_step(w, st.wsum, st.resample)) { st.selected = leaf_edge; st.edge_w = w; }
         } else {
             const EdgeNodeP &nd = edge_node(es, ref);
             const int tree = ref & kEdgeTreeBit;
@@ -1085,20 +1022,9 @@ template <int NS> struct SecEdgePickNWalk {
         }
         return st.sp == 0;
     }
-    // weight, point on the edge and edge vector of the selected edge (src/edge.cpp:1319-1363); the NEE segment
-    // is rebuilt from the slot rather than carried through the walk
     RDR_DEV_FN void finish(State &st) const {
-        const SceneD &sc = a.sc; const EdgeSceneD &es = a.es;
         if (st.idx < 0) return;
-        SecPick out{-1, 0.0, v3(0), v3(0)};
-        if (st.selected != -1) {
-            SecPre s = sec_prepare(sc, es, a.rng_main, a.dim_main, a.rng_edge, a.dim_edge, a.v, a.active[st.idx], st.idx);
-            double ew = 0;
-            V3 sample_p = v3(0), mwt = v3(0);
-            int eid = finish_edge_nee(sc, es, s.nee, s.nee_valid, s.nee_pt, s.nee_shape, st.selected, st.edge_w, st.wsum, ew, sample_p, mwt);
-            out = SecPick{eid, ew, sample_p, mwt};
-        }
-        picks[st.idx] = out;
+        picks[st.idx] = nee_pick_tail(a, st.idx, st.selected, st.edge_w, st.wsum);
     }
 };
 
@@ -1240,21 +1166,9 @@ RDR_FN SecPick gather_replay(const SecEdgeArgs &a, int idx, const GatherCand *li
         }
         const GatherCand cd = list[best];
         last_rank = best_rank;
-        const double prev = wsum;
-        wsum += cd.w;
-        const double nw = cd.w / wsum;
-        if (resample <= nw || prev == 0) { selected = cd.eid; edge_w = cd.w; resample /= nw; }
-        else resample = (resample - nw) / (1 - nw);
+        if (reservoir_step(cd.w, wsum, resample)) { selected = cd.eid; edge_w = cd.w; }
     }
-    SecPick out{-1, 0.0, v3(0), v3(0)};
-    if (selected != -1) {
-        SecPre s = sec_prepare(a.sc, a.es, a.rng_main, a.dim_main, a.rng_edge, a.dim_edge, a.v, a.active[idx], idx);
-        double ew = 0;
-        V3 sample_p = v3(0), mwt = v3(0);
-        int eid = finish_edge_nee(a.sc, a.es, s.nee, s.nee_valid, s.nee_pt, s.nee_shape, selected, edge_w, wsum, ew, sample_p, mwt);
-        out = SecPick{eid, ew, sample_p, mwt};
-    }
-    return out;
+    return nee_pick_tail(a, idx, selected, edge_w, wsum);
 }
 
 template <int NS> struct SecEdgeGatherN {
