@@ -291,7 +291,35 @@ int rdr_compute_num_channels(const int *channels, int num_channels, int max_gene
  *   - Visibility is a CONSTANT of the adjoint: rdr_deferred_shade_backward multiplies by the saved bits -- a light whose bit is 0
  *     adds nothing to the texel's gradient nor to its own -- and produces no gradient across a shadow boundary (shadows are hard
  *     and their edges are not differentiated).
- * Both fields NULL (a zeroed tail): no shadows, the same launches and the same bits as before the fields existed. */
+ * Both fields NULL (a zeroed tail): no shadows, the same launches and the same bits as before the fields existed.
+ *
+ * AMBIENT OCCLUSION (not in the reference): with `ao_occluders`, the SKY rows of the light table -- RDR_DL_AMBIENT and
+ * RDR_DL_SH_R / _G / _B, the rows that cast no shadow ray -- are dimmed by what is near the texel.  Every texel of an occluded
+ * image casts K = ao_rays any-hit rays (1 .. 32), cosine-distributed about its shading normal, that end after ao_radius; with
+ * o = popcount(word) / K, the fraction that escapes, a sky row adds o times what it adds without occlusion.  Point, directional
+ * and spot rows are untouched: shadows are their business.  The two features are independent, and all four combinations work.
+ * The rule, in fp32 (csrc/deferred.h: ao_ray, ao_directions):
+ *   - A texel casts iff nn = n.n satisfies 0 < nn < inf and every float of p, of nh = n / sqrtf(nn) and of the ray is finite;
+ *     background texels (normal 0) never cast.  A texel that does not cast has all K bits set: o = 1.
+ *   - Local directions: a table l[16][K][3] computed on the HOST in fp64 and rounded once to fp32 (no trigonometry runs in a
+ *     kernel): for ray r of rotation j, u1 = (r + 0.5) / K, u2 = the base-2 radical inverse of r, phi = 2 pi (u2 + (j + 0.5) / 16),
+ *     l = (sqrt(u1) cos phi, sqrt(u1) sin phi, sqrt(1 - u1)); l.z >= sqrt(0.5 / K) >= 0.125.  The rotation of a texel is
+ *     j = (x & 3) + 4 (y & 3), x and y its column and row in its own image of the G-buffer.  (The half step keeps phi off 0:
+ *     a local direction with a component of exactly 0 gives, about an axis-aligned normal, a ray that the conservative box test
+ *     of the traversal culls almost nothing for.)
+ *   - Frame (Duff et al.): s = copysignf(1, nh.z), a = -1 / (s + nh.z), b = (nh.x nh.y) a, T = (1 + ((s nh.x) nh.x) a, s b,
+ *     -(s nh.x)), B = (b, s + (nh.y nh.y) a, -nh.y).
+ *   - Ray: dir[k] = (l.x T[k] + l.y B[k]) + l.z nh[k], origin p, tmin = 1e-3f, tmax = ao_radius.
+ *   - Forward: a sky row's contribution is formed into a zeroed c[3], then rgb[k] += o * c[k], o = (float)popcount / (float)K;
+ *     every other row accumulates as without occlusion, in the same order over the lights.
+ *   - Occlusion is a CONSTANT of the adjoint: rdr_deferred_shade_backward calls a sky row's adjoint with o * w in place of the
+ *     upstream gradient w (the texel's gradient and the row's own are both scaled; alpha is untouched), reads the saved words,
+ *     traces nothing and needs no scene.  Nothing is differentiated through o.  With o == 1 both calls give the bits of the
+ *     call without occlusion.
+ *   - Errors, raised before anything is launched: ao_rays outside 1 .. 32 when either ao pointer is given; ao_radius that is
+ *     not > 0 (NaN included; forward); one of the pair without the other (forward); an ao_words pointer that is not 4-byte
+ *     aligned; a scene on another device than gpu_index.  The limit of 32 lights is that of SHADOWED images only.
+ * A zeroed tail: no occlusion, the same launches and the same bits as before the fields existed. */
 enum rdr_deferred_light_type { RDR_DL_AMBIENT = 0, RDR_DL_POINT = 1, RDR_DL_DIRECTIONAL = 2, RDR_DL_SPOT = 3,
                                RDR_DL_SH_R = 4, RDR_DL_SH_G = 5, RDR_DL_SH_B = 6 };
 typedef struct rdr_deferred_desc {
@@ -309,6 +337,16 @@ typedef struct rdr_deferred_desc {
                                            rdr_deferred_shade_backward reads them and needs no scene.  Bits of ambient lights, of SH rows and
                                            of lights that cast no ray at the texel are 1; bits at and above the length of the
                                            image's range are 0. */
+    const rdr_scene *const *ao_occluders; /* HOST [num_images], or NULL: no ambient occlusion.  ao_occluders[n] == NULL: image n
+                                           is not occluded and every bit of its words is set.  May name other scenes than
+                                           `occluders`.  Every scene must live on device gpu_index (harness: host). */
+    uint32_t *ao_words;                 /* DEV [num_images][height * aa_samples][width * aa_samples], required iff
+                                           ao_occluders != NULL (forward) / may be given alone (backward).  Bit r of a word:
+                                           hemisphere ray r of the texel escaped, or the texel cast none; bits at and above
+                                           ao_rays are 0.  rdr_deferred_shade writes every word; rdr_deferred_shade_backward
+                                           reads them and needs no scene. */
+    int ao_rays;                        /* K, 1 .. 32: hemisphere rays per texel */
+    float ao_radius;                    /* > 0, +inf allowed: where the rays end */
 } rdr_deferred_desc;
 int rdr_deferred_shade(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params, float *image);
 int rdr_deferred_shade_backward(const rdr_deferred_desc *desc, const float *g_buffer, const float *light_params,

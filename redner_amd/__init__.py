@@ -4,7 +4,9 @@
     redner_amd.render_pytorch    RenderFunction (torch.autograd.Function) + minimal scene classes
     redner_amd.render_utils      render_deferred + the deferred lights, render_g_buffer / render_albedo /
                                  render_pathtracing / render_generic; all exported here:
-                                 `from redner_amd import render_deferred, PointLight`
+                                 `from redner_amd import render_deferred, PointLight`; shadows (`shadows=True`) for the
+                                 point, spot and directional lights and ambient occlusion (`ambient_occlusion=K, ao_radius=r`)
+                                 for the AmbientLights and SHLights, both traced on the path tracer's any-hit kernels
     redner_amd.texture           mip-mapped Texture / EnvironmentMap and generate_mipmap on the native pyramid kernels:
                                  `from redner_amd import Texture, EnvironmentMap, generate_mipmap`; envmap_sampling_tables:
                                  the sampling tables of an environment map by one native call

@@ -139,7 +139,9 @@ class DeferredDesc(C.Structure):
     _fields_ = [('num_images', C.c_int), ('height', C.c_int), ('width', C.c_int),
                 ('aa_samples', C.c_int), ('alpha', C.c_int), ('num_lights', C.c_int),
                 ('light_type', c_int_p), ('image_light_range', c_int_p), ('gpu_index', C.c_int),
-                ('occluders', C.POINTER(C.c_void_p)), ('visibility', C.c_void_p)]     # shadows; zeroed = none
+                ('occluders', C.POINTER(C.c_void_p)), ('visibility', C.c_void_p),      # shadows; zeroed = none
+                ('ao_occluders', C.POINTER(C.c_void_p)), ('ao_words', C.c_void_p),     # ambient occlusion; zeroed = none
+                ('ao_rays', C.c_int), ('ao_radius', C.c_float)]
 
 
 # rdr_deferred_light_type

@@ -41,6 +41,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace rdr {
@@ -222,6 +223,62 @@ RDR_DEV_FN bool shadow_ray(int type, const float *lp, const Texel &t, rt::RayRec
 RDR_DEV_FN bool light_reaches(uint32_t word, int b) { return b >= 32 || ((word >> b) & 1u) != 0; }
 RDR_FN uint32_t full_mask(int len) { return len >= 32 ? 0xffffffffu : ((1u << len) - 1u); }
 
+// ---- ambient occlusion: the K hemisphere rays of a texel, its occlusion word and the factor on the sky rows --------------------
+// THE RULE (fp32 unless said otherwise).  The SKY rows of the light table are the ambient row and the SH rows: the rows that cast
+// no shadow ray.  With occlusion, a texel casts K any-hit rays (1 <= K <= 32) over the occluder scene; bit r of its word is set
+// iff ray r found no triangle in (tmin, tmax) or the texel did not cast; bits at and above K are 0.  o = popcount(word) / K
+// multiplies what the sky rows add to the texel; the other rows are untouched (shadows are their business).
+//   which texels cast   nn = n.n (n[0] n[0] + n[1] n[1] + n[2] n[2], left to right) with 0 < nn < inf, every float of p finite,
+//                       every float of nh = n / sqrtf(nn) finite and every float of the ray finite.  Background texels (normal 0),
+//                       a normal whose nn underflows to 0 or overflows, a NaN anywhere: no ray, all K bits set, o = 1.
+//   local directions    a table l[16][K][3] the HOST computes in fp64 and rounds once to fp32 (ao_directions below; no
+//                       trigonometry runs in a kernel): for ray r of rotation j,  u1 = (r + 0.5) / K,  u2 = the base-2 radical
+//                       inverse of r,  phi = 2 pi (u2 + (j + 0.5) / 16),  l = (sqrt(u1) cos phi, sqrt(u1) sin phi, sqrt(1 - u1)):
+//                       cosine-distributed, l.z >= sqrt(0.5 / K) >= 0.125, so no ray is tangent.  The rotation of a texel is
+//                       j = (x & 3) + 4 (y & 3), x and y its column and row in ITS image of the G-buffer (not in the chunk).
+//                       The HALF step in phi keeps phi off 0, where sin phi is exactly 0: about an axis-aligned normal (a wall, a
+//                       floor) such a ray has a direction component of exactly 0, and the conservative slab test (raytri.h:
+//                       ray_box_once) accepts every box whose slab the origin lies outside of -- the ray walks most of the
+//                       hierarchy.  With phi = 0 in the table (ray 0 of rotation 0), the any-hit launch of a 256^2 call on bunny_box
+//                       (1 M rays, K = 4) took 26 ms; with the half step it takes 0.16 ms (profiles/deferred_ao.txt).
+//   frame               the branch-free basis of Duff et al. about nh:  s = copysignf(1, nh.z),  a = -1 / (s + nh.z),
+//                       b = (nh.x nh.y) a,  T = (1 + ((s nh.x) nh.x) a,  s b,  -(s nh.x)),  B = (b,  s + (nh.y nh.y) a,  -nh.y);
+//                       defined at nh = (0, 0, -1).
+//   ray                 dir[k] = (l.x T[k] + l.y B[k]) + l.z nh[k];  origin p,  tmin = 1e-3f (the shadow rays' offset),
+//                       tmax = ao_radius (+inf allowed).
+//   forward             a sky row's contribution is formed by light_shade into a zeroed c[3], then rgb[k] += o * c[k];
+//                       o = (float)popcount(word) / (float)K.  Every other row accumulates as without occlusion, in the same order.
+//   adjoint             light_adjoint of a sky row takes o * w[k] in place of the upstream gradient w[k], in both passes (the
+//                       texel's gradient and the row's own); alpha is untouched.  o is a CONSTANT: nothing is differentiated
+//                       through it, and the backward call reads the saved words and traces nothing.
+// With o == 1 both forms give the bits of the call without occlusion (1 * c == c; 0 + c == c, -0 included: the sums start at +0).
+constexpr int kAoRotations = 16, kAoMaxRays = 32;
+// ray r (local direction l) of texel t: false where the texel does not cast
+RDR_DEV_FN bool ao_ray(const Texel &t, const float *l, float tmax, rt::RayRec &rec) {
+    const float nn = dot3(t.n, t.n);
+    if (!(nn > 0.f) || !finite_f(nn)) return false;
+    const float len = sqrtf(nn);
+    float nh[3];
+    for (int k = 0; k < 3; ++k) nh[k] = t.n[k] / len;
+    const float s = copysignf(1.f, nh[2]);
+    const float a = -1.f / (s + nh[2]);
+    const float b = (nh[0] * nh[1]) * a;
+    const float sx = s * nh[0];
+    const float T[3] = {1.f + (sx * nh[0]) * a, s * b, -sx};
+    const float B[3] = {b, s + (nh[1] * nh[1]) * a, -nh[1]};
+    float dir[3];
+    for (int k = 0; k < 3; ++k) dir[k] = (l[0] * T[k] + l[1] * B[k]) + l[2] * nh[k];
+    for (int k = 0; k < 3; ++k)
+        if (!finite_f(t.p[k]) || !finite_f(nh[k]) || !finite_f(dir[k])) return false;
+    rec.ox = t.p[0]; rec.oy = t.p[1]; rec.oz = t.p[2]; rec.tmin = kShadowOffset;
+    rec.dx = dir[0]; rec.dy = dir[1]; rec.dz = dir[2]; rec.tmax = tmax;
+    return true;
+}
+// (Whether a texel casts does not depend on l: |l| = 1, and with a finite nh the frame is finite -- |s + nh.z| >= 1 -- so
+// |dir[k]| <= 3.  The cast list is therefore made once for all K rays, with the table's first direction.)
+RDR_DEV_FN float ao_factor(uint32_t word, int rays) { return (float)__builtin_popcount(word) / (float)rays; }
+RDR_FN bool sky_row(int type) { return casts_no_ray(type); }
+
 // Adjoint of light_shade for the texel's upstream gradient w[3]: adds the texel's gradient to dt and, when PARAMS, the ten
 // parameter gradients to part.  (The two passes of the adjoint kernel each use one half; the other is dead code there.)
 template <bool PARAMS>
@@ -338,22 +395,35 @@ RDR_DEV_FN const uint32_t *visibility_row(const View &v, const uint32_t *vis, in
 // One OUTPUT pixel of image n: shade its aa x aa texels by the lights [lb, le), average, write 3 | 4 floats.
 // SHADOWED (here and in the two adjoint bodies): a light whose bit in the texel's word of `vis` is 0 is skipped; the plain
 // instantiation never looks at `vis` and is the code it was before there were shadows.
-template <int C, bool SHADOWED = false>
-RDR_DEV_FN void shade_pixel(const View &v, int n, int pix, int lb, int le, float *image, const uint32_t *vis = nullptr) {
+// OCCLUDED (likewise): the sky rows are scaled by the factor of the texel's word of `ao` (K = ao_rays), by the rule above; the
+// instantiations without it never look at `ao`.
+struct Occlusion { const uint32_t *words; int rays; };
+template <int C, bool SHADOWED = false, bool OCCLUDED = false>
+RDR_DEV_FN void shade_pixel(const View &v, int n, int pix, int lb, int le, float *image, const uint32_t *vis = nullptr,
+                            Occlusion ao = Occlusion{nullptr, 0}) {
     const int y = pix / v.width, x = pix - y * v.width;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int ty = 0; ty < v.aa; ++ty) {
         const float *row = texel_row<C>(v, n, y, x, ty);
         const uint32_t *vrow = SHADOWED ? visibility_row(v, vis, n, y, x, ty) : nullptr;
+        const uint32_t *arow = OCCLUDED ? visibility_row(v, ao.words, n, y, x, ty) : nullptr;
         for (int tx = 0; tx < v.aa; ++tx) {
             Texel t;
             float alpha;
             load_texel<C>(row + tx * C, t, alpha);
             float rgb[3] = {0.f, 0.f, 0.f};
             const uint32_t word = SHADOWED ? vrow[tx] : 0u;
+            const float o = OCCLUDED ? ao_factor(arow[tx], ao.rays) : 1.f;
             for (int l = lb; l < le; ++l) {
                 if (SHADOWED && !light_reaches(word, l - lb)) continue;
-                light_shade(v.type[l], v.params + (size_t)l * kLightParams, t, rgb);
+                const int type = v.type[l];
+                if (OCCLUDED && sky_row(type)) {
+                    float c[3] = {0.f, 0.f, 0.f};
+                    light_shade(type, v.params + (size_t)l * kLightParams, t, c);
+                    for (int k = 0; k < 3; ++k) rgb[k] += o * c[k];
+                    continue;
+                }
+                light_shade(type, v.params + (size_t)l * kLightParams, t, rgb);
             }
             for (int k = 0; k < 3; ++k) acc[k] += rgb[k];
             acc[3] += alpha;
@@ -384,9 +454,9 @@ RDR_DEV_FN void load_upstream(const View &v, int n, int pix, const float *d_imag
 }
 
 // Adjoint, pass 1: the gradient of every texel of one output pixel (each texel belongs to exactly one pixel: plain stores).
-template <int C, bool SHADOWED = false>
+template <int C, bool SHADOWED = false, bool OCCLUDED = false>
 RDR_DEV_FN void adjoint_pixel_texels(const View &v, int n, int pix, int lb, int le, const float *d_image, float *d_g,
-                                     const uint32_t *vis = nullptr) {
+                                     const uint32_t *vis = nullptr, Occlusion ao = Occlusion{nullptr, 0}) {
     const int y = pix / v.width, x = pix - y * v.width;
     float w[4];
     load_upstream<C>(v, n, pix, d_image, w);
@@ -394,15 +464,28 @@ RDR_DEV_FN void adjoint_pixel_texels(const View &v, int n, int pix, int lb, int 
         const float *row = texel_row<C>(v, n, y, x, ty);
         float *drow = d_g + (row - v.g);
         const uint32_t *vrow = SHADOWED ? visibility_row(v, vis, n, y, x, ty) : nullptr;
+        const uint32_t *arow = OCCLUDED ? visibility_row(v, ao.words, n, y, x, ty) : nullptr;
         for (int tx = 0; tx < v.aa; ++tx) {
             Texel t, dt;
             float alpha;
             load_texel<C>(row + tx * C, t, alpha);
             for (int k = 0; k < 3; ++k) dt.p[k] = dt.n[k] = dt.a[k] = 0.f;
             const uint32_t word = SHADOWED ? vrow[tx] : 0u;
+            float wo[3] = {0.f, 0.f, 0.f};       // o * w, the upstream gradient of the sky rows
+            if (OCCLUDED) {
+                const float o = ao_factor(arow[tx], ao.rays);
+                for (int k = 0; k < 3; ++k) wo[k] = o * w[k];
+            }
             for (int l = lb; l < le; ++l) {
                 if (SHADOWED && !light_reaches(word, l - lb)) continue;
-                light_adjoint<false>(v.type[l], v.params + (size_t)l * kLightParams, t, w, dt, nullptr);
+                const int type = v.type[l];
+                if (OCCLUDED) {                  // (values, not a pointer, are selected: the arrays stay in registers)
+                    const bool sky = sky_row(type);
+                    const float wl[3] = {sky ? wo[0] : w[0], sky ? wo[1] : w[1], sky ? wo[2] : w[2]};
+                    light_adjoint<false>(type, v.params + (size_t)l * kLightParams, t, wl, dt, nullptr);
+                    continue;
+                }
+                light_adjoint<false>(type, v.params + (size_t)l * kLightParams, t, w, dt, nullptr);
             }
             float *o = drow + tx * C;
             if (C == 10) {
@@ -417,23 +500,31 @@ RDR_DEV_FN void adjoint_pixel_texels(const View &v, int n, int pix, int lb, int 
 }
 
 // Adjoint, pass 2: what one output pixel adds to the ten parameter gradients of light l.
-template <int C, bool SHADOWED = false>
+template <int C, bool SHADOWED = false, bool OCCLUDED = false>
 RDR_DEV_FN void adjoint_pixel_light(const View &v, int n, int pix, int l, const float *d_image, double *part,
-                                    const uint32_t *vis = nullptr, int lb = 0) {
+                                    const uint32_t *vis = nullptr, int lb = 0, Occlusion ao = Occlusion{nullptr, 0}) {
     const int y = pix / v.width, x = pix - y * v.width;
     float w[4];
     load_upstream<C>(v, n, pix, d_image, w);
     const int type = v.type[l];
     const float *lp = v.params + (size_t)l * kLightParams;
+    const bool scaled = OCCLUDED && sky_row(type);       // (uniform: one light per trip of the kernel's outer loop)
     for (int ty = 0; ty < v.aa; ++ty) {
         const float *row = texel_row<C>(v, n, y, x, ty);
         const uint32_t *vrow = SHADOWED ? visibility_row(v, vis, n, y, x, ty) : nullptr;
+        const uint32_t *arow = OCCLUDED ? visibility_row(v, ao.words, n, y, x, ty) : nullptr;
         for (int tx = 0; tx < v.aa; ++tx) {
             if (SHADOWED && !light_reaches(vrow[tx], l - lb)) continue;
             Texel t, dt;
             float alpha;
             load_texel<C>(row + tx * C, t, alpha);
             for (int k = 0; k < 3; ++k) dt.p[k] = dt.n[k] = dt.a[k] = 0.f;
+            if (OCCLUDED) {                      // (one call site: 1 * w is w exactly for the rows that are not scaled)
+                const float o = scaled ? ao_factor(arow[tx], ao.rays) : 1.f;
+                const float wo[3] = {o * w[0], o * w[1], o * w[2]};
+                light_adjoint<true>(type, lp, t, wo, dt, part);
+                continue;
+            }
             light_adjoint<true>(type, lp, t, w, dt, part);
         }
     }
@@ -442,16 +533,17 @@ RDR_DEV_FN void adjoint_pixel_light(const View &v, int n, int pix, int l, const 
 #if !defined(RDR_HOSTSIM)
 // ---- gfx950 kernels --------------------------------------------------------------------------------------------------------
 // grid = (blocks per image, N): the light range of a block is uniform, so the table is read through scalar loads.
-template <int C, bool SHADOWED>
+template <int C, bool SHADOWED, bool OCCLUDED>
 __global__ void __launch_bounds__(256) deferred_shade_kernel(const float *__restrict__ g, const float *__restrict__ params,
                                                              const int *__restrict__ type, const int *__restrict__ range, int height,
                                                              int width, int aa, float *__restrict__ image,
-                                                             const uint32_t *__restrict__ vis) {
+                                                             const uint32_t *__restrict__ vis, const uint32_t *__restrict__ ao,
+                                                             int ao_rays) {
     const View v{g, params, type, range, height, width, aa};
     const int n = blockIdx.y, pixels = v.height * v.width;
     const int lb = v.range[2 * n], le = v.range[2 * n + 1];
     for (int pix = blockIdx.x * 256 + threadIdx.x; pix < pixels; pix += gridDim.x * 256)
-        shade_pixel<C, SHADOWED>(v, n, pix, lb, le, image, vis);
+        shade_pixel<C, SHADOWED, OCCLUDED>(v, n, pix, lb, le, image, vis, Occlusion{ao, ao_rays});
 }
 
 // The grid is capped (kAdjointBlocks) and strides over the pixels.  Pass 1 writes the texel gradients.  Pass 2 loops over the
@@ -460,26 +552,27 @@ __global__ void __launch_bounds__(256) deferred_shade_kernel(const float *__rest
 // the wave (DPP), across the four waves through LDS, and the block writes
 // ONE row of the slab [blocks][slab_stride]: no atomics, and a fixed summation order (deferred_fold_kernel).
 constexpr int kAdjointBlocks = 2048;
-template <int C, bool SHADOWED>
+template <int C, bool SHADOWED, bool OCCLUDED>
 __global__ void __launch_bounds__(256, 4) deferred_adjoint_kernel(const float *__restrict__ g, const float *__restrict__ params,
                                                                const int *__restrict__ type, const int *__restrict__ range, int height,
                                                                int width, int aa, const float *__restrict__ d_image,
                                                                float *__restrict__ d_g, double *__restrict__ slab, int slab_stride,
-                                                               const uint32_t *__restrict__ vis) {
+                                                               const uint32_t *__restrict__ vis, const uint32_t *__restrict__ ao,
+                                                               int ao_rays) {
     // (the tables as `restrict` arguments: the stores of pass 1 cannot alias them, so their loads stay scalar)
     const View v{g, params, type, range, height, width, aa};
     const int n = blockIdx.y, pixels = v.height * v.width;
     const int lb = v.range[2 * n], le = v.range[2 * n + 1];
     const int first = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
     for (int pix = first; pix < pixels; pix += step)
-        adjoint_pixel_texels<C, SHADOWED>(v, n, pix, lb, le, d_image, d_g, vis);
+        adjoint_pixel_texels<C, SHADOWED, OCCLUDED>(v, n, pix, lb, le, d_image, d_g, vis, Occlusion{ao, ao_rays});
     __shared__ double wave_part[4][kLightParams];
     double *row = slab + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * slab_stride;
     for (int l = lb; l < le; ++l) {
         double part[kLightParams];
         for (int k = 0; k < kLightParams; ++k) part[k] = 0.0;
         for (int pix = first; pix < pixels; pix += step)
-            adjoint_pixel_light<C, SHADOWED>(v, n, pix, l, d_image, part, vis, lb);
+            adjoint_pixel_light<C, SHADOWED, OCCLUDED>(v, n, pix, l, d_image, part, vis, lb, Occlusion{ao, ao_rays});
         for (int k = 0; k < kLightParams; ++k) part[k] = wave_sum(part[k]);         // every lane is active here
         if ((threadIdx.x & 63) == 0)
             for (int k = 0; k < kLightParams; ++k) wave_part[threadIdx.x >> 6][k] = part[k];
@@ -650,24 +743,134 @@ inline void cast_shadows(const rdr_deferred_desc &d, const View &v, uint32_t *vi
     }
 }
 
-template <int C, bool SHADOWED>
-inline void shade_impl(const rdr_deferred_desc &d, const View &v, float *image, const uint32_t *vis) {
+// ---- ambient occlusion: the occlusion words of a call ----------------------------------------------------------------------------
+// ONE pass per (occluded image, chunk of texels), whatever K is -- all K rays of a chunk's texels go into one queue, so the
+// launches of a call do not grow with K (small frames are launch-bound: profiles/deferred_shadows.txt).  A chunk holds
+// shadow_chunk() / K texels, so the scratch (list 4 bytes per texel, rays 32 + hits 8 bytes per ray) is bounded by the chunk:
+//   compact_dev         the texels of the chunk that cast (ao_ray) -> list, once for all K rays; `live` stays on the device
+//   exec::scaled_count  one lane: K * live, the device count of the queue
+//   AoRays              one lane per ray; the queue is RAY-MAJOR, slot r * live + i is ray r of listed texel i, so neighbouring
+//                       slots hold the same local direction (up to the rotation) of neighbouring texels
+//   exec::trace         any-hit, trimmed by the device's count
+//   AoMark              one lane per listed texel: reads its K hits and stores the whole word -- no read-modify-write
+// The host reads no count back.
+template <int C>
+struct CastsAoRays {
+    const float *texels; const float *dirs;
+    RDR_DEV_FN bool operator()(int i) const {
+        Texel t;
+        float alpha;
+        load_texel<C>(texels + (size_t)i * C, t, alpha);
+        rt::RayRec rec;
+        return ao_ray(t, dirs, 1.f, rec);
+    }
+};
+// `first_texel`: the chunk's first texel, counted within its image (the rotation goes by the texel's place in the image);
+// `wg`: texels per row of the image; `dirs`: the table [16][K][3]
+template <int C>
+struct AoRays {
+    const float *texels; const int *list; const int *live; int live_upper; const float *dirs; int rays; float tmax;
+    unsigned first_texel, wg; rt::RayRec *queue;
+    RDR_DEV_FN void operator()(int slot) const {
+        const int c = *live, count = c < live_upper ? c : live_upper;      // (slot < rays * count: count > 0)
+        const int r = slot / count, i = slot - r * count;
+        const int item = list[i];
+        Texel t;
+        float alpha;
+        load_texel<C>(texels + (size_t)item * C, t, alpha);
+        const unsigned at = first_texel + (unsigned)item, y = at / wg, x = at - y * wg;
+        const int j = (int)((x & 3u) + 4u * (y & 3u));
+        rt::RayRec rec;
+        if (!ao_ray(t, dirs + ((size_t)j * rays + r) * 3, tmax, rec)) {    // (the list holds only texels that cast; a moot ray all the same)
+            rec.ox = rec.oy = rec.oz = rec.tmin = rec.dx = rec.dy = rec.dz = 0.f;
+            rec.tmax = -1.f;
+        }
+        F4 *out = reinterpret_cast<F4 *>(queue + slot);
+        out[0] = F4{rec.ox, rec.oy, rec.oz, rec.tmin};
+        out[1] = F4{rec.dx, rec.dy, rec.dz, rec.tmax};
+    }
+};
+struct AoMark {
+    const int *list; const int *live; int live_upper; const rt::HitRec *hits; uint32_t *words; int rays;
+    RDR_DEV_FN void operator()(int i) const {
+        const int c = *live, count = c < live_upper ? c : live_upper;
+        uint32_t word = 0u;
+        for (int r = 0; r < rays; ++r)
+            if (hits[(size_t)r * count + i].shape < 0) word |= 1u << r;
+        words[list[i]] = word;
+    }
+};
+// The local directions by the rule above: fp64 on the host, rounded once
+inline std::vector<float> ao_directions(int rays) {
+    std::vector<float> table((size_t)kAoRotations * rays * 3);
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int j = 0; j < kAoRotations; ++j)
+        for (int r = 0; r < rays; ++r) {
+            double u2 = 0.0, digit = 0.5;
+            for (unsigned b = (unsigned)r; b; b >>= 1, digit *= 0.5)
+                if (b & 1u) u2 += digit;
+            const double u1 = (r + 0.5) / rays, phi = two_pi * (u2 + (j + 0.5) / 16.0);
+            float *l = table.data() + ((size_t)j * rays + r) * 3;
+            l[0] = (float)(std::sqrt(u1) * std::cos(phi));
+            l[1] = (float)(std::sqrt(u1) * std::sin(phi));
+            l[2] = (float)std::sqrt(1.0 - u1);
+        }
+    return table;
+}
+
+template <int C>
+inline void cast_occlusion(const rdr_deferred_desc &d, const View &v, Arena &arena) {
+    const size_t texels = (size_t)d.height * d.aa_samples * (size_t)d.width * d.aa_samples;       // validate: at most 2e8
+    const int rays = d.ao_rays;
+    const int per_chunk = shadow_chunk() / rays > 0 ? shadow_chunk() / rays : 1;
+    const int chunk = texels < (size_t)per_chunk ? (int)texels : per_chunk;
+    const unsigned wg = (unsigned)d.width * (unsigned)d.aa_samples;
+    int *list = nullptr;
+    rt::RayRec *queue = nullptr;
+    rt::HitRec *hits = nullptr;
+    const float *dirs = nullptr;
+    for (int n = 0; n < d.num_images; ++n) {
+        uint32_t *words = d.ao_words + (size_t)n * texels;
+        exec::launch((int)texels, FillWords{words, full_mask(rays)});
+        if (!d.ao_occluders[n]) continue;
+        const Scene &scene = *reinterpret_cast<const Scene *>(d.ao_occluders[n]);
+        if (!list) {
+            const std::vector<float> table = ao_directions(rays);
+            dirs = arena.put(table.data(), table.size());
+            list = arena.get<int>((size_t)chunk);
+            queue = arena.get<rt::RayRec>((size_t)chunk * rays);
+            hits = arena.get<rt::HitRec>((size_t)chunk * rays);
+        }
+        for (size_t base = 0; base < texels; base += (size_t)chunk) {
+            const int count = texels - base < (size_t)chunk ? (int)(texels - base) : chunk;
+            const float *first = v.g + ((size_t)n * texels + base) * C;
+            const exec::Count live = exec::compact_dev(nullptr, exec::Count(count), list, CastsAoRays<C>{first, dirs});
+            const exec::Count all = exec::scaled_count(live, rays);
+            exec::launch(all, AoRays<C>{first, list, live.dev, live.upper, dirs, rays, d.ao_radius, (unsigned)base, wg, queue});
+            exec::trace(scene.bvh, queue, hits, all, true);
+            exec::launch(live, AoMark{list, live.dev, live.upper, hits, words + base, rays});
+        }
+    }
+}
+
+template <int C, bool SHADOWED, bool OCCLUDED>
+inline void shade_impl(const rdr_deferred_desc &d, const View &v, float *image, const uint32_t *vis, Occlusion ao) {
     const int pixels = d.height * d.width;
 #if !defined(RDR_HOSTSIM)
     const dim3 grid((pixels + 255) / 256, d.num_images);
-    hipLaunchKernelGGL((deferred_shade_kernel<C, SHADOWED>), grid, dim3(256), 0, exec::ctx().stream, v.g, v.params, v.type, v.range,
-                       v.height, v.width, v.aa, image, vis);
+    hipLaunchKernelGGL((deferred_shade_kernel<C, SHADOWED, OCCLUDED>), grid, dim3(256), 0, exec::ctx().stream, v.g, v.params, v.type,
+                       v.range, v.height, v.width, v.aa, image, vis, ao.words, ao.rays);
     exec::check(hipGetLastError(), "deferred_shade launch");
 #else
     for (int n = 0; n < d.num_images; ++n)
         for (int pix = 0; pix < pixels; ++pix)
-            shade_pixel<C, SHADOWED>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], image, vis);
+            shade_pixel<C, SHADOWED, OCCLUDED>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], image, vis, ao);
 #endif
 }
 
-template <int C, bool SHADOWED>
+template <int C, bool SHADOWED, bool OCCLUDED>
 inline void adjoint_impl(const rdr_deferred_desc &d, const View &v, const float *d_image, float *d_g, float *d_params,
-                         const uint32_t *vis) {
+                         const uint32_t *vis, Occlusion ao) {
     const int pixels = d.height * d.width;
 #if !defined(RDR_HOSTSIM)
     int per_image = (pixels + 255) / 256;
@@ -681,8 +884,9 @@ inline void adjoint_impl(const rdr_deferred_desc &d, const View &v, const float 
     const int slab_stride = longest * kLightParams;
     Arena arena;
     double *slab = arena.get<double>((size_t)per_image * d.num_images * (slab_stride > 0 ? slab_stride : 1));
-    hipLaunchKernelGGL((deferred_adjoint_kernel<C, SHADOWED>), dim3(per_image, d.num_images), dim3(256), 0, exec::ctx().stream, v.g,
-                       v.params, v.type, v.range, v.height, v.width, v.aa, d_image, d_g, slab, slab_stride, vis);
+    hipLaunchKernelGGL((deferred_adjoint_kernel<C, SHADOWED, OCCLUDED>), dim3(per_image, d.num_images), dim3(256), 0,
+                       exec::ctx().stream, v.g, v.params, v.type, v.range, v.height, v.width, v.aa, d_image, d_g, slab, slab_stride, vis,
+                       ao.words, ao.rays);
     exec::check(hipGetLastError(), "deferred_shade_adjoint launch");
     if (d.num_lights > 0) {
         hipLaunchKernelGGL(deferred_fold_kernel, dim3(d.num_lights), dim3(256), 0, exec::ctx().stream, slab, slab_stride, per_image,
@@ -693,12 +897,13 @@ inline void adjoint_impl(const rdr_deferred_desc &d, const View &v, const float 
 #else
     for (int n = 0; n < d.num_images; ++n)
         for (int pix = 0; pix < pixels; ++pix)
-            adjoint_pixel_texels<C, SHADOWED>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], d_image, d_g, vis);
+            adjoint_pixel_texels<C, SHADOWED, OCCLUDED>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], d_image, d_g, vis, ao);
     for (int l = 0; l < d.num_lights; ++l) {
         double part[kLightParams] = {0};
         for (int n = 0; n < d.num_images; ++n) {
             if (l < v.range[2 * n] || l >= v.range[2 * n + 1]) continue;
-            for (int pix = 0; pix < pixels; ++pix) adjoint_pixel_light<C, SHADOWED>(v, n, pix, l, d_image, part, vis, v.range[2 * n]);
+            for (int pix = 0; pix < pixels; ++pix)
+                adjoint_pixel_light<C, SHADOWED, OCCLUDED>(v, n, pix, l, d_image, part, vis, v.range[2 * n], ao);
         }
         for (int k = 0; k < kLightParams; ++k) d_params[l * kLightParams + k] = (float)part[k];
     }
@@ -727,6 +932,40 @@ inline void validate_shadows(const rdr_deferred_desc &d, bool forward, const cha
     }
 }
 
+// ... and the four occlusion fields, likewise.  The limit of 32 lights is the visibility word's: an occluded image may have more.
+inline void validate_occlusion(const rdr_deferred_desc &d, bool forward, const char *who) {
+    auto fail = [&](const std::string &what) { throw std::runtime_error(std::string(who) + ": " + what); };
+    if (!d.ao_occluders && !d.ao_words) return;
+    if (d.ao_rays < 1 || d.ao_rays > kAoMaxRays) fail("ao_rays must be 1 .. 32, got " + std::to_string(d.ao_rays));
+    if (forward && d.ao_occluders && !d.ao_words) fail("ao_occluders need an ao_words buffer");
+    if (forward && !d.ao_occluders && d.ao_words) fail("an ao_words buffer needs ao_occluders");
+    if (d.ao_words && ((uintptr_t)d.ao_words & 3)) fail("the ao_words buffer must be 4-byte aligned");
+    if (!forward) return;
+    if (!(d.ao_radius > 0.f)) fail("ao_radius must be positive (+inf: unbounded), got " + std::to_string(d.ao_radius));
+#if !defined(RDR_HOSTSIM)
+    for (int n = 0; n < d.num_images; ++n) {
+        if (!d.ao_occluders[n]) continue;
+        const int at = reinterpret_cast<const Scene *>(d.ao_occluders[n])->gpu_index;
+        if (at != d.gpu_index)
+            fail("the ao occluder scene of image " + std::to_string(n) + " lives on device " + std::to_string(at) +
+                 ", the call runs on device " + std::to_string(d.gpu_index));
+    }
+#endif
+}
+
+// The instantiation a call asks for: F is called with (C, SHADOWED, OCCLUDED) as integral constants
+template <class F>
+inline void dispatch(bool alpha, bool shadowed, bool occluded, const F &f) {
+    using std::integral_constant;
+    auto by_mode = [&](auto c) {
+        if (shadowed && occluded) f(c, integral_constant<bool, true>(), integral_constant<bool, true>());
+        else if (shadowed) f(c, integral_constant<bool, true>(), integral_constant<bool, false>());
+        else if (occluded) f(c, integral_constant<bool, false>(), integral_constant<bool, true>());
+        else f(c, integral_constant<bool, false>(), integral_constant<bool, false>());
+    };
+    if (alpha) by_mode(integral_constant<int, 10>()); else by_mode(integral_constant<int, 9>());
+}
+
 // rdr_deferred_shade: synchronised on return
 inline void shade(const rdr_deferred_desc &d, const float *g, const float *params, float *image) {
     validate(d, "rdr_deferred_shade");
@@ -734,16 +973,17 @@ inline void shade(const rdr_deferred_desc &d, const float *g, const float *param
     if (d.alpha && (((uintptr_t)g & 7) || ((uintptr_t)image & 15)))
         throw std::runtime_error("rdr_deferred_shade: with alpha the G-buffer must be 8-byte and the image 16-byte aligned");
     validate_shadows(d, true, "rdr_deferred_shade");
+    validate_occlusion(d, true, "rdr_deferred_shade");
     Tables tables(d);
     const View v = make_view(d, tables, g, params);
-    if (d.occluders) {
-        Arena scratch;                     // back in the pool after the upload_flush below
-        if (d.alpha) { cast_shadows<10>(d, v, d.visibility, scratch); shade_impl<10, true>(d, v, image, d.visibility); }
-        else { cast_shadows<9>(d, v, d.visibility, scratch); shade_impl<9, true>(d, v, image, d.visibility); }
-        exec::upload_flush();
-        return;
-    }
-    if (d.alpha) shade_impl<10, false>(d, v, image, nullptr); else shade_impl<9, false>(d, v, image, nullptr);
+    Arena scratch;                         // (empty without shadows and occlusion) back in the pool after the upload_flush below
+    const Occlusion ao{d.ao_words, d.ao_rays};
+    dispatch(d.alpha != 0, d.occluders != nullptr, d.ao_occluders != nullptr, [&](auto c, auto shadowed, auto occluded) {
+        constexpr int C = decltype(c)::value;
+        if (shadowed) cast_shadows<C>(d, v, d.visibility, scratch);
+        if (occluded) cast_occlusion<C>(d, v, scratch);
+        shade_impl<C, decltype(shadowed)::value, decltype(occluded)::value>(d, v, image, d.visibility, ao);
+    });
     exec::upload_flush();
 }
 
@@ -757,14 +997,14 @@ inline void shade_backward(const rdr_deferred_desc &d, const float *g, const flo
     if (d.alpha && ((((uintptr_t)g | (uintptr_t)d_g) & 7) || ((uintptr_t)d_image & 15)))
         throw std::runtime_error("rdr_deferred_shade_backward: with alpha the G-buffers must be 8-byte and the image gradient 16-byte aligned");
     validate_shadows(d, false, "rdr_deferred_shade_backward");
+    validate_occlusion(d, false, "rdr_deferred_shade_backward");
     Tables tables(d);
     const View v = make_view(d, tables, g, params);
-    const uint32_t *vis = d.visibility;
-    if (vis) {
-        if (d.alpha) adjoint_impl<10, true>(d, v, d_image, d_g, d_params, vis); else adjoint_impl<9, true>(d, v, d_image, d_g, d_params, vis);
-    } else {
-        if (d.alpha) adjoint_impl<10, false>(d, v, d_image, d_g, d_params, nullptr); else adjoint_impl<9, false>(d, v, d_image, d_g, d_params, nullptr);
-    }
+    const Occlusion ao{d.ao_words, d.ao_rays};      // the saved words: occlusion, like visibility, is a constant of the adjoint
+    dispatch(d.alpha != 0, d.visibility != nullptr, d.ao_words != nullptr, [&](auto c, auto shadowed, auto occluded) {
+        adjoint_impl<decltype(c)::value, decltype(shadowed)::value, decltype(occluded)::value>(d, v, d_image, d_g, d_params,
+                                                                                                 d.visibility, ao);
+    });
     exec::upload_flush();
 }
 

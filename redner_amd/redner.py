@@ -421,8 +421,20 @@ class DeferredLightType(enum.IntEnum):     # rdr_deferred_light_type (not in the
     sh_b = _capi.DL_SH_B
 
 
+def _scene_handles(scenes, num_images, what):
+    """one Scene (or None) per image -> the table of handles, which lives as long as the call"""
+    scenes = list(scenes)
+    if len(scenes) != num_images:
+        raise RuntimeError('redner.deferred_shade: %d %s scenes for %d images' % (len(scenes), what, num_images))
+    lib = _capi.lib()
+    for sc in scenes:
+        if sc is not None and (not isinstance(sc, Scene) or sc._handle is None or sc._lib is not lib):
+            raise RuntimeError('redner.deferred_shade: an %s must be a live Scene of the loaded library, or None' % what)
+    return (C.c_void_p * max(len(scenes), 1))(*[None if sc is None else sc._handle for sc in scenes]), scenes
+
+
 def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
-                   occluders=None, visibility=None):
+                   occluders=None, visibility=None, ao_occluders=None, ao_words=None, ao_rays=0, ao_radius=float('inf')):
     d = _capi.DeferredDesc()
     d.num_images, d.height, d.width = int(num_images), int(height), int(width)
     d.aa_samples, d.alpha, d.num_lights = int(aa_samples), int(bool(alpha)), len(light_types)
@@ -433,41 +445,44 @@ def _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, im
     ranges = (C.c_int32 * max(len(flat), 1))(*flat)
     d.light_type, d.image_light_range = types, ranges
     d.gpu_index = _gpu_index(use_gpu, gpu_index)
-    handles = None
-    if occluders is not None:              # one Scene (or None: not shadowed) per image; the table lives as long as the call
-        occluders = list(occluders)
-        if len(occluders) != d.num_images:
-            raise RuntimeError('redner.deferred_shade: %d occluder scenes for %d images' % (len(occluders), d.num_images))
-        lib = _capi.lib()
-        for sc in occluders:
-            if sc is not None and (not isinstance(sc, Scene) or sc._handle is None or sc._lib is not lib):
-                raise RuntimeError('redner.deferred_shade: an occluder must be a live Scene of the loaded library, or None')
-        handles = (C.c_void_p * max(len(occluders), 1))(*[None if sc is None else sc._handle for sc in occluders])
+    handles = ao_handles = None
+    if occluders is not None:              # one Scene (or None: not shadowed) per image
+        handles, occluders = _scene_handles(occluders, d.num_images, 'occluder')
         d.occluders = handles
     if visibility is not None:
         d.visibility = _ptr(visibility)
-    return d, (types, ranges, handles, occluders)
+    if ao_occluders is not None:           # ... (or None: not occluded)
+        ao_handles, ao_occluders = _scene_handles(ao_occluders, d.num_images, 'ao occluder')
+        d.ao_occluders = ao_handles
+    if ao_words is not None:
+        d.ao_words = _ptr(ao_words)
+    d.ao_rays, d.ao_radius = int(ao_rays), float(ao_radius)
+    return d, (types, ranges, handles, occluders, ao_handles, ao_occluders)
 
 
 def deferred_shade(g_buffer, light_params, image, num_images, height, width, aa_samples, alpha, light_types,
-                   image_light_ranges, use_gpu, gpu_index, occluders=None, visibility=None):
+                   image_light_ranges, use_gpu, gpu_index, occluders=None, visibility=None, ao_occluders=None, ao_words=None,
+                   ao_rays=0, ao_radius=float('inf')):
     """Not in the reference: rdr_deferred_shade (include/redner_amd.h).  g_buffer [N, H * aa, W * aa, 9 + alpha],
     light_params [L, 10], image [N, H, W, 3 + alpha]: float_ptr; light_types: L DeferredLightType; image_light_ranges: N
     (begin, end) pairs into the table.  Shadows: `occluders`, N Scenes (None: that image is not shadowed), and `visibility`,
-    int_ptr to [N, H * aa, W * aa] 32-bit words, every one of which is written (bit b: light begin + b reaches the texel)."""
+    int_ptr to [N, H * aa, W * aa] 32-bit words, every one of which is written (bit b: light begin + b reaches the texel).
+    Ambient occlusion of the ambient and SH rows: `ao_occluders`, N Scenes (None: that image is not occluded), `ao_words`, int_ptr
+    to words of the same shape, every one written (bit r: hemisphere ray r of the texel escaped), `ao_rays` 1 .. 32 per texel
+    and `ao_radius` > 0, where they end."""
     d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
-                              occluders, visibility)
+                              occluders, visibility, ao_occluders, ao_words, ao_rays, ao_radius)
     _call(_capi.lib(), 'deferred_shade', 'rdr_deferred_shade', C.byref(d), _ptr(g_buffer), _ptr(light_params), _ptr(image),
           on=(use_gpu, gpu_index))
 
 
 def deferred_shade_backward(g_buffer, light_params, d_image, d_g_buffer, d_light_params, num_images, height, width,
                             aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index, occluders=None,
-                            visibility=None):
+                            visibility=None, ao_occluders=None, ao_words=None, ao_rays=0, ao_radius=float('inf')):
     """Not in the reference: rdr_deferred_shade_backward; writes every element of d_g_buffer and d_light_params.  `visibility`:
-    the words the forward call wrote, held constant (no scene is needed)."""
+    the words the forward call wrote, held constant (no scene is needed); `ao_words` with `ao_rays` likewise."""
     d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
-                              occluders, visibility)
+                              occluders, visibility, ao_occluders, ao_words, ao_rays, ao_radius)
     _call(_capi.lib(), 'deferred_shade_backward', 'rdr_deferred_shade_backward', C.byref(d), _ptr(g_buffer), _ptr(light_params),
           _ptr(d_image), _ptr(d_g_buffer), _ptr(d_light_params), on=(use_gpu, gpu_index))
 

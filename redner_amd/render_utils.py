@@ -43,8 +43,16 @@ coefficients or the normals.  In the light table an SHLight is three rows, one p
 Shadows (`render_deferred(..., shadows=True)`, `deferred_shade(..., occluders=...)`; not in the reference): every texel casts one
 any-hit shadow ray per point, spot and directional light over the scene's triangles, on the path tracer's traversal kernels and
 with its 1e-3 offsets; a blocked light adds nothing to the texel.  Shadows are hard, and visibility is a constant of the gradient.
-Ambient lights and SHLights cast no shadow ray: occluders never dim them.  A shadowed image may have at most 32 rows in the
+Ambient lights and SHLights cast no shadow ray: occluders dim them through ambient occlusion only (below).  A shadowed image may have at most 32 rows in the
 light table: one per light, three per SHLight.
+
+Ambient occlusion (`render_deferred(..., ambient_occlusion=K, ao_radius=r)`, `deferred_shade(..., ambient_occlusion=K)`; not in
+the reference): how occluders dim an AmbientLight and an SHLight.  Every texel casts K any-hit rays (1 .. 32),
+cosine-distributed about its shading normal, that end after `ao_radius`; the fraction o that escapes multiplies what the ambient
+lights and SHLights add to the texel.  Point, directional and spot lights are untouched -- shadows are their business -- and the
+two features are independent.  The directions are a fixed table (a radical-inverse spiral, rotated by the texel's place in a
+4 x 4 tile; include/redner_amd.h states the rule), so two calls give the same bits.  Occlusion, like visibility, is a constant of
+the gradient: the backward call reads the saved words and traces nothing.  The limit of 32 rows does not apply to it.
 """
 import random
 from typing import List, Optional, Union
@@ -197,12 +205,17 @@ def _aligned(t, alpha):
 
 class DeferredShade(torch.autograd.Function):
     """apply(g_buffer [N, H * aa, W * aa, 9 + alpha], light_params [L, 10], light_types, image_light_ranges, aa_samples, alpha,
-    backend, occluders) -> [N, H, W, 3 + alpha].  One native launch forward, one (+ the fold of the light gradients) backward.
+    backend, occluders, ao_scenes, ao_rays, ao_radius) -> [N, H, W, 3 + alpha].  One native launch forward, one (+ the fold of the
+    light gradients) backward.
     `occluders`: None, or N `backend.Scene` (None: that image is not shadowed) -- the shadow rays of the forward call are traced
-    over them; the [N, H * aa, W * aa] visibility words are saved for the backward call, which needs no scene."""
+    over them; the [N, H * aa, W * aa] visibility words are saved for the backward call, which needs no scene.
+    `ao_scenes`: None, or N `backend.Scene` (None: that image is not occluded) -- `ao_rays` hemisphere rays per texel, ending after
+    `ao_radius`, are traced over them; the [N, H * aa, W * aa] occlusion words follow the image (and the visibility words, when
+    there are any) and are saved likewise."""
 
     @staticmethod
-    def forward(ctx, g_buffer, light_params, light_types, image_light_ranges, aa_samples, alpha, backend=None, occluders=None):
+    def forward(ctx, g_buffer, light_params, light_types, image_light_ranges, aa_samples, alpha, backend=None, occluders=None,
+                ao_scenes=None, ao_rays=0, ao_radius=float('inf')):
         rd = backend or _default_backend
         light_types = tuple(int(t) for t in light_types)
         image_light_ranges = tuple((int(b), int(e)) for b, e in image_light_ranges)
@@ -222,6 +235,8 @@ class DeferredShade(torch.autograd.Function):
             raise RuntimeError('DeferredShade: %d light ranges for %d images' % (len(image_light_ranges), n))
         if occluders is not None and len(occluders) != n:
             raise RuntimeError('DeferredShade: %d occluder scenes for %d images' % (len(occluders), n))
+        if ao_scenes is not None and len(ao_scenes) != n:
+            raise RuntimeError('DeferredShade: %d ao occluder scenes for %d images' % (len(ao_scenes), n))
         if g_buffer.dtype != torch.float32 or light_params.dtype != torch.float32:
             raise RuntimeError('DeferredShade: fp32 tensors only')
         device = g_buffer.device
@@ -232,35 +247,43 @@ class DeferredShade(torch.autograd.Function):
         image = torch.empty(n, h, w, 3 + int(alpha), dtype=torch.float32, device=device)
         geometry = (n, h, w, aa_samples, alpha, light_types, image_light_ranges, use_gpu, index)
         ctx.rd, ctx.geometry, ctx.params_device = rd, geometry, light_params.device
-        if occluders is None:
+        if occluders is None and ao_scenes is None:
             rd.deferred_shade(ptr(rd, g), ptr(rd, params), ptr(rd, image), *geometry)
-            ctx.shadowed = False
+            ctx.shadowed, ctx.ao_rays = False, 0
             ctx.save_for_backward(g, params)
             return image
-        visibility = torch.empty(n, hg, wg, dtype=torch.int32, device=device)        # every word is written
-        rd.deferred_shade(ptr(rd, g), ptr(rd, params), ptr(rd, image), *geometry, occluders=tuple(occluders),
-                          visibility=rd.int_ptr(visibility.data_ptr()))
-        ctx.shadowed = True
-        ctx.save_for_backward(g, params, visibility)
-        ctx.mark_non_differentiable(visibility)
-        return image, visibility
+        words, keywords = [], {}                   # the word tensors in the order they are returned and saved
+        if occluders is not None:
+            words.append(torch.empty(n, hg, wg, dtype=torch.int32, device=device))       # every word is written
+            keywords.update(occluders=tuple(occluders), visibility=rd.int_ptr(words[-1].data_ptr()))
+        if ao_scenes is not None:
+            words.append(torch.empty(n, hg, wg, dtype=torch.int32, device=device))
+            keywords.update(ao_occluders=tuple(ao_scenes), ao_words=rd.int_ptr(words[-1].data_ptr()), ao_rays=int(ao_rays),
+                            ao_radius=float(ao_radius))
+        rd.deferred_shade(ptr(rd, g), ptr(rd, params), ptr(rd, image), *geometry, **keywords)
+        ctx.shadowed, ctx.ao_rays = occluders is not None, int(ao_rays) if ao_scenes is not None else 0
+        ctx.save_for_backward(g, params, *words)
+        ctx.mark_non_differentiable(*words)
+        return (image, *words)
 
     @staticmethod
-    def backward(ctx, grad_img, grad_visibility=None):
+    def backward(ctx, grad_img, *grad_words):
         rd, geometry = ctx.rd, ctx.geometry
         saved = ctx.saved_tensors
-        g, params = saved[0], saved[1]
+        g, params, words = saved[0], saved[1], list(saved[2:])
         alpha = geometry[4]
         grad_img = _aligned(upstream(grad_img, g.device), alpha)
         assert torch.isfinite(grad_img).all()
         d_g = torch.empty_like(g)
         d_params = torch.empty_like(params)
+        keywords = {}
         if ctx.shadowed:
-            rd.deferred_shade_backward(ptr(rd, g), ptr(rd, params), ptr(rd, grad_img), ptr(rd, d_g), ptr(rd, d_params), *geometry,
-                                       visibility=rd.int_ptr(saved[2].data_ptr()))
-        else:
-            rd.deferred_shade_backward(ptr(rd, g), ptr(rd, params), ptr(rd, grad_img), ptr(rd, d_g), ptr(rd, d_params), *geometry)
-        return d_g, d_params.to(ctx.params_device), None, None, None, None, None, None
+            keywords.update(visibility=rd.int_ptr(words.pop(0).data_ptr()))
+        if ctx.ao_rays:
+            keywords.update(ao_words=rd.int_ptr(words.pop(0).data_ptr()), ao_rays=ctx.ao_rays)
+        rd.deferred_shade_backward(ptr(rd, g), ptr(rd, params), ptr(rd, grad_img), ptr(rd, d_g), ptr(rd, d_params), *geometry,
+                                   **keywords)
+        return d_g, d_params.to(ctx.params_device), None, None, None, None, None, None, None, None, None
 
 
 class OccluderScene:
@@ -284,13 +307,29 @@ def occluder_scene(scene, device: Optional[torch.device] = None, backend=None):
     return OccluderScene(u.scene, (u, args))
 
 
-def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None, occluders=None, return_visibility=False):
+def _per_image_scenes(occluders, n, which='occluders'):
+    """None, one occluder_scene for all images or a list of N of them (None entries allowed) -> N backend Scenes or None.
+    `which`: the argument of deferred_shade they came in by, for the error"""
+    if occluders is None or not isinstance(occluders, (list, tuple)):
+        occluders = [occluders] * n
+    elif len(occluders) != n:
+        raise RuntimeError('deferred_shade: %s holds %d occluder scenes for %d images' % (which, len(occluders), n))
+    return tuple(o.scene if isinstance(o, OccluderScene) else o for o in occluders)
+
+
+def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None, occluders=None, return_visibility=False,
+                   ambient_occlusion=0, ao_radius=float('inf'), ao_occluders=None, return_occlusion=False):
     """Shade a stack of G-buffers [N, H * aa, W * aa, 9 + alpha] in one launch.  `lights`: one list of DeferredLight shared by
     the N images, or N lists.  `occluders`: None (no shadows), one `occluder_scene(...)` for all images, or a list of N of them
     (None: that image is not shadowed); a shadowed image may have at most 32 lights, three per SHLight (they count by their rows
     in the table, although they cast no shadow).  Shadows are hard and are held constant by
     the gradient.  `return_visibility`: also the [N, H * aa, W * aa] int32 words, bit b = light b of the image's list reaches the
-    texel (all lights, when there are no occluders)."""
+    texel (all lights, when there are no occluders).
+    `ambient_occlusion`: K in 1 .. 32 hemisphere rays per texel, ending after `ao_radius` (> 0), dim the ambient lights and
+    SHLights by the fraction that is blocked; 0: none.  They are traced over `ao_occluders` (given like `occluders`) or, when
+    that is None, over `occluders`: pass `ao_occluders=` alone for occlusion without shadows.  `return_occlusion`: also the
+    [N, H * aa, W * aa] int32 words, bit r = ray r of the texel escaped.  Results come in the order image, visibility,
+    occlusion, each extra only when asked for.  Occlusion is held constant by the gradient."""
     n = int(g_buffer.shape[0])
     per_image = len(lights) > 0 and isinstance(lights[0], (list, tuple))
     if per_image:
@@ -304,15 +343,31 @@ def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None, oc
     else:
         flat, ranges = list(lights), [(0, _num_rows(lights))] * n
     params, types = pack_lights(flat, g_buffer.device)
-    if occluders is None and not return_visibility:
-        return DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend)
-    if occluders is None or not isinstance(occluders, (list, tuple)):
-        occluders = [occluders] * n
-    elif len(occluders) != n:
-        raise RuntimeError('render_deferred: %d occluder scenes for %d images' % (len(occluders), n))
-    scenes = tuple(o.scene if isinstance(o, OccluderScene) else o for o in occluders)        # (`occluders` lives through the call)
-    image, visibility = DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend, scenes)
-    return (image, visibility) if return_visibility else image
+    ambient_occlusion = int(ambient_occlusion)
+    if ambient_occlusion == 0 and not return_occlusion:
+        if occluders is None and not return_visibility:
+            return DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend)
+        scenes = _per_image_scenes(occluders, n)                                          # (`occluders` lives through the call)
+        image, visibility = DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend, scenes)
+        return (image, visibility) if return_visibility else image
+    if ambient_occlusion < 0 or ambient_occlusion > 32:
+        raise RuntimeError('deferred_shade: ambient_occlusion must be 0 (off) or 1 .. 32 rays per texel, got %d' % ambient_occlusion)
+    if ambient_occlusion > 0 and ao_occluders is None and occluders is None:
+        raise RuntimeError('deferred_shade: ambient_occlusion needs ao_occluders or occluders to trace its rays over')
+    if ambient_occlusion > 0:
+        ao_scenes = _per_image_scenes(occluders, n) if ao_occluders is None else _per_image_scenes(ao_occluders, n, 'ao_occluders')
+        rays = ambient_occlusion
+    else:                                      # only the words were asked for: nothing is occluded, one ray that escapes
+        ao_scenes, rays = (None,) * n, 1
+    scenes = _per_image_scenes(occluders, n) if occluders is not None or return_visibility else None
+    out = DeferredShade.apply(g_buffer, params, tuple(types), tuple(ranges), aa_samples, alpha, backend, scenes, ao_scenes, rays,
+                              float(ao_radius))
+    results = [out[0]]
+    if return_visibility:
+        results.append(out[1])
+    if return_occlusion:
+        results.append(out[-1])
+    return tuple(results) if len(results) > 1 else results[0]
 
 
 def _default_device(device):
@@ -353,7 +408,8 @@ def _render_g_buffer_for_deferred(scene, seed, channels, aa_samples, sample_pixe
 
 def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = False, aa_samples: int = 2, seed=None,
                     sample_pixel_center: bool = False, use_primary_edge_sampling: bool = True,
-                    device: Optional[torch.device] = None, backend=None, shadows: bool = False):
+                    device: Optional[torch.device] = None, backend=None, shadows: bool = False, ambient_occlusion: int = 0,
+                    ao_radius: float = float('inf')):
     """Deferred rendering: Lambertian shading of the G-buffer by `lights`.
 
     scene: a Scene -> [H, W, 3 | 4]; a list of N scenes of one resolution -> [N, H, W, 3 | 4], shaded in one launch.
@@ -364,7 +420,12 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
     point, spot and directional light over the triangles of its scene, with the path tracer's offsets (the ray starts 1e-3 along
     its direction and, for a light with a position, ends at (1 - 1e-3) of the distance); a light that is blocked adds nothing.
     Shadows are HARD and are not differentiated across their boundary: the gradient holds visibility constant (DESIGN.md
-    section 7).  At most 32 lights per scene, three per SHLight; ambient lights and SHLights are not shadowed."""
+    section 7).  At most 32 lights per scene, three per SHLight; ambient lights and SHLights are not shadowed.
+    `ambient_occlusion` (redner_amd extension), independent of `shadows`: K in 1 .. 32 any-hit rays per texel, cosine-distributed
+    about the shading normal and ending after `ao_radius`, over the triangles of its scene; the fraction that escapes multiplies
+    what the AmbientLights and SHLights add (the other lights are untouched).  Held constant by the gradient, like visibility.
+    WARNING: in a closed scene, such as a box around the objects, every unbounded ray is blocked and the ambient lights go
+    black: give a finite `ao_radius` there, a fraction of the scene's size."""
     backend = backend or _default_backend
     device = _default_device(device)
     aa_samples = int(aa_samples)
@@ -381,8 +442,11 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
                                                device, backend) for sc, se in zip(scenes, seeds)]
     g_buffer = g_buffers[0].unsqueeze(0) if single else torch.stack(g_buffers)
     # (the occluder scenes live until the shade call has returned)
-    occluders = [occluder_scene(sc, device=device, backend=backend) for sc in scenes] if shadows else None
-    images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend, occluders=occluders)
+    ambient_occlusion = int(ambient_occlusion)
+    built = [occluder_scene(sc, device=device, backend=backend) for sc in scenes] if shadows or ambient_occlusion else None
+    images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend,
+                            occluders=built if shadows else None, ambient_occlusion=ambient_occlusion, ao_radius=ao_radius,
+                            ao_occluders=built if ambient_occlusion else None)
     return images[0] if single else images
 
 
