@@ -6,7 +6,9 @@
                                  render_pathtracing / render_generic; all exported here:
                                  `from redner_amd import render_deferred, PointLight`; shadows (`shadows=True`) for the
                                  point, spot and directional lights and ambient occlusion (`ambient_occlusion=K, ao_radius=r`)
-                                 for the AmbientLights and SHLights, both traced on the path tracer's any-hit kernels
+                                 for the AmbientLights and SHLights, both traced on the path tracer's any-hit kernels;
+                                 specular highlights (`specular=True`, `deferred_specular`): the specular lobe of the path
+                                 tracer's BSDF under the point, spot and directional lights, one native kernel and its adjoint
     redner_amd.texture           mip-mapped Texture / EnvironmentMap and generate_mipmap on the native pyramid kernels:
                                  `from redner_amd import Texture, EnvironmentMap, generate_mipmap`; envmap_sampling_tables:
                                  the sampling tables of an environment map by one native call
@@ -28,7 +30,7 @@
 import sys
 
 _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'SHLight', 'DeferredShade',
-                 'deferred_shade', 'occluder_scene', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo',
+                 'deferred_shade', 'DeferredSpecular', 'deferred_specular', 'occluder_scene', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo',
                  'render_pathtracing')
 _TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid', 'envmap_sampling_tables')
 _UTILS = ('SH_reconstruct', 'SHReconstruct')

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in include/redner_amd.h and its companion headers (redner_amd_mesh.h, _image.h, _pose.h, _debug.h).
+"""ctypes binding of the C ABI in include/redner_amd.h and its companion headers (redner_amd_mesh.h, _image.h, _pose.h, _debug.h;
+csrc/deferred_specular_abi.h).
 
 The shared library is the product: `redner_amd/lib/libredner_amd.so`, built by
 `__graft_entry__.build()` (hipcc, gfx950).  If it is missing the import fails loudly -- there is
@@ -224,6 +225,14 @@ HEADERS = {
     },
 }
 
+# Companion headers that stand under redner_amd/csrc/ (the set of files under include/ is fixed): bound by load() like HEADERS
+CSRC_HEADERS = {
+    'deferred_specular_abi.h': {             # specular highlights in deferred shading (csrc/deferred_specular.h)
+        'rdr_deferred_specular': (_i, [C.POINTER(DeferredDesc), _p, _p, _p, _p, _p]),
+        'rdr_deferred_specular_backward': (_i, [C.POINTER(DeferredDesc)] + [_p] * 9),
+    },
+}
+
 # rdr_scatter_op / rdr_scatter_target (rdr_debug_grad_scatter)
 SCATTER_ACCUM, SCATTER_ACCUM_TEXEL, SCATTER_ACCUM_PLAIN, SCATTER_ACCUM_TRIPLE, SCATTER_ACCUM_TEXEL_TRIPLE, \
     SCATTER_TRIGRAD_WAVE, SCATTER_POSITIONS_WAVE = range(7)
@@ -245,7 +254,7 @@ def load(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % path)
     lib = C.CDLL(path)
-    signatures = [item for table in HEADERS.values() for item in table.items()]
+    signatures = [item for table in list(HEADERS.values()) + list(CSRC_HEADERS.values()) for item in table.items()]
     for name, _ in signatures:
         if not hasattr(lib, name):
             raise RuntimeError("redner_amd: %s does not export %s" % (path, name))

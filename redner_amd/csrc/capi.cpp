@@ -6,6 +6,8 @@
 #include "trace_plan.h"
 #include "edges.h"
 #include "deferred.h"
+#include "deferred_specular_abi.h"
+#include "deferred_specular.h"
 #include "mipmap.h"
 #include "vertex_normal.h"
 #include "mesh_smooth.h"
@@ -198,6 +200,26 @@ int rdr_deferred_shade_backward(const rdr_deferred_desc *desc, const float *g_bu
         if (!desc) throw std::runtime_error("rdr_deferred_shade_backward: a description is required");
         OnDevice on(desc->gpu_index);
         rdr::dfr::shade_backward(*desc, g_buffer, light_params, d_image, d_g_buffer, d_light_params);
+    });
+}
+
+int rdr_deferred_specular(const rdr_deferred_desc *desc, const float *g_buffer, const float *material, const float *eye,
+                          const float *light_params, float *image) {
+    return status([&] {
+        if (!desc) throw std::runtime_error("rdr_deferred_specular: a description is required");
+        OnDevice on(desc->gpu_index);
+        rdr::dfs::specular(*desc, g_buffer, material, eye, light_params, image);
+    });
+}
+
+int rdr_deferred_specular_backward(const rdr_deferred_desc *desc, const float *g_buffer, const float *material, const float *eye,
+                                   const float *light_params, const float *d_image, float *d_g_buffer, float *d_material,
+                                   float *d_eye, float *d_light_params) {
+    return status([&] {
+        if (!desc) throw std::runtime_error("rdr_deferred_specular_backward: a description is required");
+        OnDevice on(desc->gpu_index);
+        rdr::dfs::specular_backward(*desc, g_buffer, material, eye, light_params, d_image, d_g_buffer, d_material, d_eye,
+                                    d_light_params);
     });
 }
 

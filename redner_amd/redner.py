@@ -487,6 +487,29 @@ def deferred_shade_backward(g_buffer, light_params, d_image, d_g_buffer, d_light
           _ptr(d_image), _ptr(d_g_buffer), _ptr(d_light_params), on=(use_gpu, gpu_index))
 
 
+def deferred_specular(g_buffer, material, eye, light_params, image, num_images, height, width, aa_samples, alpha, light_types,
+                      image_light_ranges, use_gpu, gpu_index, visibility=None):
+    """Not in the reference: rdr_deferred_specular (csrc/deferred_specular_abi.h).  g_buffer [N, H * aa, W * aa, 9 + alpha],
+    material [N, H * aa, W * aa, 4] (ks rgb, roughness), eye [N, 3], light_params [L, 10], image [N, H, W, 3]: float_ptr; the
+    table as for deferred_shade.  `visibility`: int_ptr to the words deferred_shade wrote, read only."""
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
+                              visibility=visibility)
+    _call(_capi.lib(), 'deferred_specular', 'rdr_deferred_specular', C.byref(d), _ptr(g_buffer), _ptr(material), _ptr(eye),
+          _ptr(light_params), _ptr(image), on=(use_gpu, gpu_index))
+
+
+def deferred_specular_backward(g_buffer, material, eye, light_params, d_image, d_g_buffer, d_material, d_eye, d_light_params,
+                               num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
+                               visibility=None):
+    """Not in the reference: rdr_deferred_specular_backward; writes every element of d_g_buffer, d_material, d_eye and
+    d_light_params.  `visibility`: the words of the forward call, held constant."""
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, light_types, image_light_ranges, use_gpu, gpu_index,
+                              visibility=visibility)
+    _call(_capi.lib(), 'deferred_specular_backward', 'rdr_deferred_specular_backward', C.byref(d), _ptr(g_buffer), _ptr(material),
+          _ptr(eye), _ptr(light_params), _ptr(d_image), _ptr(d_g_buffer), _ptr(d_material), _ptr(d_eye), _ptr(d_light_params),
+          on=(use_gpu, gpu_index))
+
+
 def mip_num_levels(height, width):
     """Not in the reference's module: rdr_mip_num_levels, min(ceil(log2(max(height, width))) + 1, 8)."""
     return int(_capi.lib().rdr_mip_num_levels(int(height), int(width)))

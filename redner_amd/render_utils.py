@@ -53,6 +53,22 @@ lights and SHLights add to the texel.  Point, directional and spot lights are un
 two features are independent.  The directions are a fixed table (a radical-inverse spiral, rotated by the texel's place in a
 4 x 4 tile; include/redner_amd.h states the rule), so two calls give the same bits.  Occlusion, like visibility, is a constant of
 the gradient: the backward call reads the saved words and traces nothing.  The limit of 32 rows does not apply to it.
+
+Specular highlights (`render_deferred(..., specular=True)`, `deferred_specular(g_buffer, material, lights, eye)`; not in the
+reference, whose deferred pass is Lambertian): the specular half of the path tracer's own BSDF -- Blinn-Phong distribution, Smith
+shadowing, Schlick Fresnel; one-sided -- under the point, spot and directional lights, as ONE native kernel and its adjoint
+(`rdr_deferred_specular`, csrc/deferred_specular.h).  Per texel with specular reflectance ks, roughness rho and the eye of its image:
+
+    nh = n / |n|,  v = (eye - p) / |eye - p|,  cv = nh.v              nothing unless n != 0 and cv > 0
+    per light:  l and E = I / d.d (point),  I * pow(max(l.s, 0), e) (spot),  I (directional);   cl = nh.l, nothing unless cl > 1e-3
+    m = (v + l) / |v + l|,  cm = nh.m                                 nothing unless cm > 0
+    r = max(rho, 1e-3),  e = max(2 / r - 2, 0),  D = pow(cm, e) * (e + 2) / (2 pi)
+    G = G1(cv) * G1(cl), Smith's rational fit at a = 1 / (sqrt(r) * tan)
+    F = k + (1 - k) * pow(max(1 - |m.l|, 0), 5),  k = max(ks, 0)
+    E * F * D * G / (4 cv)
+
+so a PointLight gives the path tracer's direct specular term for a point source.  Ambient lights and SHLights cast no highlight.
+Every clamp and the roughness floor pass half the gradient at the tie; the conditions and the visibility bits are constants.
 """
 import random
 from typing import List, Optional, Union
@@ -195,6 +211,23 @@ def pack_lights(lights, device):
     return torch.cat(pieces).reshape(len(types), _LIGHT_PARAMS), types
 
 
+def _light_table(lights, n, device):
+    """one list of lights shared by the n images, or n lists -> (params [L, 10], the L row types, the n row ranges)"""
+    per_image = len(lights) > 0 and isinstance(lights[0], (list, tuple))
+    if per_image:
+        if len(lights) != n:
+            raise RuntimeError('render_deferred: %d light lists for %d scenes' % (len(lights), n))
+        flat, ranges, rows = [], [], 0
+        for lgts in lights:                  # ranges are in ROWS of the table
+            ranges.append((rows, rows + _num_rows(lgts)))
+            rows += _num_rows(lgts)
+            flat.extend(lgts)
+    else:
+        flat, ranges = list(lights), [(0, _num_rows(lights))] * n
+    params, types = pack_lights(flat, device)
+    return params, types, ranges
+
+
 def _aligned(t, alpha):
     """contiguous fp32; with alpha the kernels use 8- / 16-byte accesses (a fresh tensor is aligned, an offset view may not be)"""
     t = t.contiguous()
@@ -331,18 +364,7 @@ def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None, oc
     [N, H * aa, W * aa] int32 words, bit r = ray r of the texel escaped.  Results come in the order image, visibility,
     occlusion, each extra only when asked for.  Occlusion is held constant by the gradient."""
     n = int(g_buffer.shape[0])
-    per_image = len(lights) > 0 and isinstance(lights[0], (list, tuple))
-    if per_image:
-        if len(lights) != n:
-            raise RuntimeError('render_deferred: %d light lists for %d scenes' % (len(lights), n))
-        flat, ranges, rows = [], [], 0
-        for lgts in lights:                  # ranges are in ROWS of the table
-            ranges.append((rows, rows + _num_rows(lgts)))
-            rows += _num_rows(lgts)
-            flat.extend(lgts)
-    else:
-        flat, ranges = list(lights), [(0, _num_rows(lights))] * n
-    params, types = pack_lights(flat, g_buffer.device)
+    params, types, ranges = _light_table(lights, n, g_buffer.device)
     ambient_occlusion = int(ambient_occlusion)
     if ambient_occlusion == 0 and not return_occlusion:
         if occluders is None and not return_visibility:
@@ -368,6 +390,92 @@ def deferred_shade(g_buffer, lights, alpha=False, aa_samples=1, backend=None, oc
     if return_occlusion:
         results.append(out[-1])
     return tuple(results) if len(results) > 1 else results[0]
+
+
+class DeferredSpecular(torch.autograd.Function):
+    """apply(g_buffer [N, H * aa, W * aa, 9 + alpha], material [N, H * aa, W * aa, 4], eye [N, 3], light_params [L, 10],
+    light_types, image_light_ranges, aa_samples, alpha, backend, visibility) -> [N, H, W, 3]: the specular lobe (module
+    docstring) of every texel under the lights of its image, averaged over each aa x aa block.  One native launch forward, one
+    (+ the fold of the light and eye gradients) backward; gradients reach the position and normal channels of the G-buffer, the
+    material, the eye and the lights.  `visibility`: None, or the [N, H * aa, W * aa] int32 words of deferred_shade -- a light
+    whose bit is clear adds nothing; the words are held constant by the gradient."""
+
+    @staticmethod
+    def forward(ctx, g_buffer, material, eye, light_params, light_types, image_light_ranges, aa_samples, alpha, backend=None,
+                visibility=None):
+        rd = backend or _default_backend
+        light_types = tuple(int(t) for t in light_types)
+        image_light_ranges = tuple((int(b), int(e)) for b, e in image_light_ranges)
+        aa_samples, alpha = int(aa_samples), bool(alpha)
+        channels = 9 + int(alpha)
+        if g_buffer.dim() != 4 or g_buffer.shape[3] != channels:
+            raise RuntimeError('DeferredSpecular: the G-buffer must be [N, H * aa, W * aa, %d], got %s'
+                               % (channels, tuple(g_buffer.shape)))
+        n, hg, wg = int(g_buffer.shape[0]), int(g_buffer.shape[1]), int(g_buffer.shape[2])
+        if aa_samples < 1 or hg % aa_samples != 0 or wg % aa_samples != 0 or n == 0 or hg == 0 or wg == 0:
+            raise RuntimeError('DeferredSpecular: a G-buffer of %d x %d x %d does not divide into aa_samples = %d blocks'
+                               % (n, hg, wg, aa_samples))
+        if tuple(material.shape) != (n, hg, wg, 4):
+            raise RuntimeError('DeferredSpecular: the material must be [%d, %d, %d, 4] (specular reflectance 3, roughness 1), got %s'
+                               % (n, hg, wg, tuple(material.shape)))
+        if tuple(eye.shape) != (n, 3):
+            raise RuntimeError('DeferredSpecular: eye must be [%d, 3], got %s' % (n, tuple(eye.shape)))
+        if tuple(light_params.shape) != (len(light_types), _LIGHT_PARAMS):
+            raise RuntimeError('DeferredSpecular: light_params must be [%d, %d], got %s'
+                               % (len(light_types), _LIGHT_PARAMS, tuple(light_params.shape)))
+        if len(image_light_ranges) != n:
+            raise RuntimeError('DeferredSpecular: %d light ranges for %d images' % (len(image_light_ranges), n))
+        if any(t.dtype != torch.float32 for t in (g_buffer, material, eye, light_params)):
+            raise RuntimeError('DeferredSpecular: fp32 tensors only')
+        device = g_buffer.device
+        if material.device != device:
+            raise RuntimeError('DeferredSpecular: the material is on %s, the G-buffer on %s' % (material.device, device))
+        if visibility is not None:
+            if tuple(visibility.shape) != (n, hg, wg) or visibility.dtype != torch.int32 or visibility.device != device:
+                raise RuntimeError('DeferredSpecular: visibility must be [%d, %d, %d] int32 on %s' % (n, hg, wg, device))
+            visibility = visibility.detach().contiguous()
+        use_gpu, index = place(device)
+        g = _aligned(g_buffer.detach(), True)                  # (16 bytes serve both widths)
+        mat = _aligned(material.detach(), True)
+        eyes = eye.detach().to(device).contiguous()
+        params = light_params.detach().to(device).contiguous()
+        h, w = hg // aa_samples, wg // aa_samples
+        image = torch.empty(n, h, w, 3, dtype=torch.float32, device=device)
+        geometry = (n, h, w, aa_samples, alpha, light_types, image_light_ranges, use_gpu, index)
+        ctx.rd, ctx.geometry, ctx.devices = rd, geometry, (eye.device, light_params.device)
+        words = None if visibility is None else rd.int_ptr(visibility.data_ptr())
+        rd.deferred_specular(ptr(rd, g), ptr(rd, mat), ptr(rd, eyes), ptr(rd, params), ptr(rd, image), *geometry, visibility=words)
+        ctx.shadowed = visibility is not None
+        ctx.save_for_backward(g, mat, eyes, params, *(() if visibility is None else (visibility,)))
+        return image
+
+    @staticmethod
+    def backward(ctx, grad_img):
+        rd, geometry = ctx.rd, ctx.geometry
+        saved = ctx.saved_tensors
+        g, mat, eyes, params = saved[:4]
+        grad_img = upstream(grad_img, g.device)
+        assert torch.isfinite(grad_img).all()
+        d_g, d_mat, d_eye, d_params = (torch.empty_like(t) for t in (g, mat, eyes, params))
+        words = rd.int_ptr(saved[4].data_ptr()) if ctx.shadowed else None
+        rd.deferred_specular_backward(ptr(rd, g), ptr(rd, mat), ptr(rd, eyes), ptr(rd, params), ptr(rd, grad_img), ptr(rd, d_g),
+                                      ptr(rd, d_mat), ptr(rd, d_eye), ptr(rd, d_params), *geometry, visibility=words)
+        return d_g, d_mat, d_eye.to(ctx.devices[0]), d_params.to(ctx.devices[1]), None, None, None, None, None, None
+
+
+def deferred_specular(g_buffer, material, lights, eye, alpha=False, aa_samples=1, visibility=None, backend=None):
+    """The specular highlights of a stack of G-buffers [N, H * aa, W * aa, 9 + alpha] -> [N, H, W, 3], to be added to the colour
+    channels of `deferred_shade`'s image.  `material` [N, H * aa, W * aa, 4]: specular reflectance rgb, then roughness (the
+    `specular_reflectance` and `roughness` channels of `render_g_buffer`); `eye` [N, 3] (or [3] for all images): where the camera
+    stands; `lights` as for `deferred_shade` -- point, spot and directional lights cast a highlight, ambient lights and SHLights
+    none.  `visibility`: the words `deferred_shade(..., return_visibility=True)` gave: a light that is blocked casts no highlight."""
+    n = int(g_buffer.shape[0])
+    params, types, ranges = _light_table(lights, n, g_buffer.device)
+    eye = torch.as_tensor(eye)
+    if eye.dim() == 1:
+        eye = eye.reshape(1, -1).expand(n, -1)
+    return DeferredSpecular.apply(g_buffer, material, eye, params, tuple(types), tuple(ranges), aa_samples, alpha, backend,
+                                  visibility)
 
 
 def _default_device(device):
@@ -406,11 +514,21 @@ def _render_g_buffer_for_deferred(scene, seed, channels, aa_samples, sample_pixe
     return RenderFunction.apply(seed, *args)
 
 
+def _eye_of(camera, backend):
+    """where a camera stands, as a tensor a gradient can reach: its position or, for one given by cam_to_world, the translation
+    column; an orthographic camera has no eye point"""
+    if int(camera.camera_type) == int(backend.CameraType.orthographic):
+        raise RuntimeError('render_deferred: specular=True needs an eye point, which an orthographic camera does not have')
+    if camera.cam_to_world is not None:
+        return camera.cam_to_world[:3, 3]
+    return torch.as_tensor(camera.position).reshape(3)
+
+
 def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = False, aa_samples: int = 2, seed=None,
                     sample_pixel_center: bool = False, use_primary_edge_sampling: bool = True,
                     device: Optional[torch.device] = None, backend=None, shadows: bool = False, ambient_occlusion: int = 0,
-                    ao_radius: float = float('inf')):
-    """Deferred rendering: Lambertian shading of the G-buffer by `lights`.
+                    ao_radius: float = float('inf'), specular: bool = False):
+    """Deferred rendering: Lambertian shading of the G-buffer by `lights` and, with `specular`, the specular lobe on top.
 
     scene: a Scene -> [H, W, 3 | 4]; a list of N scenes of one resolution -> [N, H, W, 3 | 4], shaded in one launch.
     lights: a list of DeferredLight (shared by all scenes of a batch) or, for a batch, one list per scene.
@@ -425,7 +543,13 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
     about the shading normal and ending after `ao_radius`, over the triangles of its scene; the fraction that escapes multiplies
     what the AmbientLights and SHLights add (the other lights are untouched).  Held constant by the gradient, like visibility.
     WARNING: in a closed scene, such as a box around the objects, every unbounded ray is blocked and the ambient lights go
-    black: give a finite `ao_radius` there, a fraction of the scene's size."""
+    black: give a finite `ao_radius` there, a fraction of the scene's size.
+    `specular` (redner_amd extension): the G-buffer also carries the materials' specular reflectance and roughness, and the
+    specular lobe of the path tracer's BSDF under the point, spot and directional lights (`deferred_specular`; the module
+    docstring has the formula) is added to the colour channels; with `shadows`, a blocked light casts no highlight.  The eye is
+    the camera's position (the translation column of a `cam_to_world`), so an orthographic camera raises.  Gradients reach
+    `specular_reflectance`, `roughness`, the geometry, the lights and the camera position.  Ambient occlusion leaves the
+    highlights alone.  False: the same launches and the same bits as without the argument."""
     backend = backend or _default_backend
     device = _default_device(device)
     aa_samples = int(aa_samples)
@@ -437,6 +561,9 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
         channels.append(backend.channels.alpha)
     single = isinstance(scene, Scene) or not isinstance(scene, (list, tuple))
     scenes = [scene] if single else list(scene)
+    if specular:
+        channels += [backend.channels.specular_reflectance, backend.channels.roughness]
+        eyes = [_eye_of(sc.camera, backend) for sc in scenes]
     seeds = [_random_seed() if seed is None else seed] if single else _seeds_for(scenes, seed)
     g_buffers = [_render_g_buffer_for_deferred(sc, se, channels, aa_samples, sample_pixel_center, use_primary_edge_sampling,
                                                device, backend) for sc, se in zip(scenes, seeds)]
@@ -444,9 +571,24 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
     # (the occluder scenes live until the shade call has returned)
     ambient_occlusion = int(ambient_occlusion)
     built = [occluder_scene(sc, device=device, backend=backend) for sc in scenes] if shadows or ambient_occlusion else None
-    images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend,
-                            occluders=built if shadows else None, ambient_occlusion=ambient_occlusion, ao_radius=ao_radius,
-                            ao_occluders=built if ambient_occlusion else None)
+    if not specular:
+        images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend,
+                                occluders=built if shadows else None, ambient_occlusion=ambient_occlusion, ao_radius=ao_radius,
+                                ao_occluders=built if ambient_occlusion else None)
+        return images[0] if single else images
+    # the diffuse part exactly as above on its own channels (asking for the words when there are shadows), then the lobe
+    diffuse_channels = 9 + int(bool(alpha))
+    g, material = g_buffer[..., :diffuse_channels].contiguous(), g_buffer[..., diffuse_channels:].contiguous()      # one copy each
+    out = deferred_shade(g, lights, alpha=alpha, aa_samples=aa_samples, backend=backend, occluders=built if shadows else None,
+                         return_visibility=bool(shadows), ambient_occlusion=ambient_occlusion, ao_radius=ao_radius,
+                         ao_occluders=built if ambient_occlusion else None)
+    images, visibility = out if shadows else (out, None)
+    eye = torch.stack([e.to(device=device, dtype=torch.float32) for e in eyes])
+    highlights = deferred_specular(g, material, lights, eye, alpha=alpha, aa_samples=aa_samples, visibility=visibility,
+                                   backend=backend)
+    if alpha:
+        highlights = torch.cat([highlights, torch.zeros_like(highlights[..., :1])], dim=-1)
+    images = images + highlights
     return images[0] if single else images
 
 
