@@ -28,6 +28,14 @@ def upstream(g, device):
     return None if g is None else g.to(device=device, dtype=torch.float32).contiguous()
 
 
+def first_order_only(name):
+    """First line of every native `backward`: the adjoints are kernels, which autograd cannot differentiate again.  Autograd runs
+    `backward` in grad mode exactly under create_graph=True (plain and retain_graph passes run it with grad mode off); without
+    this the first gradient would come back with requires_grad == False and a second-order term would drop out silently."""
+    if torch.is_grad_enabled():
+        raise RuntimeError('%s: the native adjoint cannot be differentiated again (create_graph=True)' % name)
+
+
 class named:
     """with named(who): a RuntimeError from inside leaves with the public function's name in front of its text (and itself as
     the cause); anything else passes."""

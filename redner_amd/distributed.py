@@ -25,6 +25,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from ._op import first_order_only
 from .render_pytorch import RenderFunction
 
 
@@ -93,7 +94,8 @@ def shard_args(args, rank, world, spp_fwd, spp_bwd):
 
 class DistributedRenderFunction(torch.autograd.Function):
     """RenderFunction whose forward image and backward gradients are reduced over the process
-    group.  Every rank must call it with the same scene and the same upstream gradient."""
+    group.  Every rank must call it with the same scene and the same upstream gradient.  Like RenderFunction's, its
+    gradients cannot be differentiated again: under create_graph=True the backward call raises."""
 
     @staticmethod
     def forward(ctx, seed, group, meta, *tensors):
@@ -103,6 +105,7 @@ class DistributedRenderFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_img):
+        first_order_only('DistributedRenderFunction')
         grads = RenderFunction.backward(ctx, grad_img)
         dev = ctx.meta['device']
         live = [g for g in grads[2:] if g is not None]

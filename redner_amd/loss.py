@@ -20,7 +20,7 @@ library raises for them.
 import torch
 
 from . import redner as _default_backend
-from ._op import named, place, ptr, scratch, upstream
+from ._op import first_order_only, named, place, ptr, scratch, upstream
 
 
 def _geometry(image):
@@ -43,7 +43,8 @@ def _forward(rd, image, target, num_levels, clamp, weights):
 
 class GaussianPyramidLoss(torch.autograd.Function):
     """image, target [H, W, C] or [N, H, W, C] fp32 -> (loss, terms): a 0-dim fp32 tensor and the fp64 [num_levels] per-level
-    terms (not differentiable), on the inputs' device.  The gradient goes to `image` and, if it asks for one, to `target`."""
+    terms (not differentiable), on the inputs' device.  The gradient goes to `image` and, if it asks for one, to `target`; it cannot be
+    differentiated again: under create_graph=True the backward call raises."""
 
     @staticmethod
     def forward(ctx, image, target, num_levels, clamp, weights, backend=None):
@@ -58,6 +59,7 @@ class GaussianPyramidLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss, _d_terms):
+        first_order_only('GaussianPyramidLoss')
         rd = ctx.rd
         a, b, saved = ctx.saved_tensors
         num_levels, clamp, weights = ctx.options

@@ -27,7 +27,7 @@ from typing import List, Optional
 import torch
 
 from . import redner as _default_backend
-from ._op import place
+from ._op import first_order_only, place
 
 
 class Camera:
@@ -171,7 +171,8 @@ def _remember_finite(t):
 
 
 class RenderFunction(torch.autograd.Function):
-    """torch.autograd.Function around redner.render (pyredner/render_pytorch.py:62-1177)."""
+    """torch.autograd.Function around redner.render (pyredner/render_pytorch.py:62-1177).  Gradients reach every floating-point
+    tensor of the scene, once: under create_graph=True the backward call raises (the adjoint render cannot be differentiated again)."""
 
     @staticmethod
     def serialize_scene(scene: Scene, num_samples, max_bounces, channels: Optional[List] = None,
@@ -436,6 +437,7 @@ class RenderFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_img):
+        first_order_only('RenderFunction')
         meta, tensors, u = ctx.meta, ctx.tensors, ctx.u
         rd = meta['backend']
         grad_img = grad_img.contiguous()

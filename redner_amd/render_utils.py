@@ -76,7 +76,7 @@ from typing import List, Optional, Union
 import torch
 
 from . import redner as _default_backend
-from ._op import place, ptr, upstream
+from ._op import first_order_only, place, ptr, upstream
 from .render_pytorch import RenderFunction, Scene
 
 _LIGHT_PARAMS = 10          # csrc/deferred.h: intensity 3, position 3, direction 3, spot exponent 1
@@ -244,7 +244,8 @@ class DeferredShade(torch.autograd.Function):
     over them; the [N, H * aa, W * aa] visibility words are saved for the backward call, which needs no scene.
     `ao_scenes`: None, or N `backend.Scene` (None: that image is not occluded) -- `ao_rays` hemisphere rays per texel, ending after
     `ao_radius`, are traced over them; the [N, H * aa, W * aa] occlusion words follow the image (and the visibility words, when
-    there are any) and are saved likewise."""
+    there are any) and are saved likewise.
+    Gradients reach the G-buffer and the light table, once: under create_graph=True the backward call raises."""
 
     @staticmethod
     def forward(ctx, g_buffer, light_params, light_types, image_light_ranges, aa_samples, alpha, backend=None, occluders=None,
@@ -301,6 +302,7 @@ class DeferredShade(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_img, *grad_words):
+        first_order_only('DeferredShade')
         rd, geometry = ctx.rd, ctx.geometry
         saved = ctx.saved_tensors
         g, params, words = saved[0], saved[1], list(saved[2:])
@@ -398,7 +400,8 @@ class DeferredSpecular(torch.autograd.Function):
     docstring) of every texel under the lights of its image, averaged over each aa x aa block.  One native launch forward, one
     (+ the fold of the light and eye gradients) backward; gradients reach the position and normal channels of the G-buffer, the
     material, the eye and the lights.  `visibility`: None, or the [N, H * aa, W * aa] int32 words of deferred_shade -- a light
-    whose bit is clear adds nothing; the words are held constant by the gradient."""
+    whose bit is clear adds nothing; the words are held constant by the gradient.  The gradients cannot be differentiated
+    again: under create_graph=True the backward call raises."""
 
     @staticmethod
     def forward(ctx, g_buffer, material, eye, light_params, light_types, image_light_ranges, aa_samples, alpha, backend=None,
@@ -451,6 +454,7 @@ class DeferredSpecular(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_img):
+        first_order_only('DeferredSpecular')
         rd, geometry = ctx.rd, ctx.geometry
         saved = ctx.saved_tensors
         g, mat, eyes, params = saved[:4]

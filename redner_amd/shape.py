@@ -28,7 +28,7 @@ import threading
 import torch
 
 from . import redner as _default_backend
-from ._op import place, ptr, scratch, upstream
+from ._op import first_order_only, place, ptr, scratch, upstream
 
 SCHEMES = {'max': 0, 'cotangent': 1}
 PLAN_CACHE_SIZE = 8
@@ -59,7 +59,8 @@ class MeshTopology:
 
 
 class VertexNormals(torch.autograd.Function):
-    """vertices [V, 3] -> normals [V, 3].  One native call forward, one backward."""
+    """vertices [V, 3] -> normals [V, 3].  One native call forward, one backward; the gradient goes to `vertices`, once: under
+    create_graph=True the backward call raises."""
 
     @staticmethod
     def forward(ctx, vertices, topology, scheme):
@@ -83,6 +84,7 @@ class VertexNormals(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_normals):
+        first_order_only('VertexNormals')
         if d_normals is None:
             return None, None, None
         topology, rd = ctx.topology, ctx.topology.rd
@@ -187,7 +189,8 @@ def bound_vertices(vertices, indices, topology=None, backend=None):
 
 
 class MeshLaplacian(torch.autograd.Function):
-    """vertices [V, 3] -> shift [V, 3] = (C / W) * control; control [V] is a constant.  One native call forward, one backward."""
+    """vertices [V, 3] -> shift [V, 3] = (C / W) * control; control [V] is a constant.  One native call forward, one backward; the
+    gradient goes to `vertices`, once: under create_graph=True the backward call raises."""
 
     @staticmethod
     def forward(ctx, vertices, topology, scheme, control):
@@ -205,6 +208,7 @@ class MeshLaplacian(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_shift):
+        first_order_only('MeshLaplacian')
         if d_shift is None:
             return None, None, None, None
         topology, rd = ctx.topology, ctx.topology.rd

@@ -33,7 +33,7 @@ import torch
 
 from . import redner as _default_backend
 from . import render_pytorch
-from ._op import named, place, ptr, scratch, upstream
+from ._op import first_order_only, named, place, ptr, scratch, upstream
 
 
 def _level_sizes(height, width, num_levels):
@@ -69,6 +69,7 @@ class MipPyramid(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *d_levels):
+        first_order_only('MipPyramid')
         rd = ctx.rd
         h, w, c, use_gpu, index = ctx.geometry
         d_texels = torch.empty(h, w, c, dtype=torch.float32, device=ctx.device)
@@ -81,7 +82,7 @@ class MipPyramid(torch.autograd.Function):
 
 def generate_mipmap(texels, backend=None):
     """The reference's pyramid of an [H, W, C] fp32 image: a list of [Hl, Wl, C] tensors, [0] being `texels.contiguous()`.
-    Differentiable: the gradients of all levels reach `texels`."""
+    Differentiable: the gradients of all levels reach `texels`.  Once: under create_graph=True the backward call raises."""
     if not isinstance(texels, torch.Tensor) or texels.dim() != 3:
         raise RuntimeError('generate_mipmap: texels must be an [H, W, C] tensor')
     base = texels.contiguous()

@@ -21,13 +21,14 @@ translation and centre are read on the device.
 import torch
 
 from . import redner as _default_backend
-from ._op import named, place, ptr, scratch, upstream
+from ._op import first_order_only, named, place, ptr, scratch, upstream
 
 MAX_SETS = 16
 
 
 class RotateMatrix(torch.autograd.Function):
-    """angles [3] fp32 -> R [3, 3] fp32 on the same device; the gradient goes to `angles`."""
+    """angles [3] fp32 -> R [3, 3] fp32 on the same device; the gradient goes to `angles`, once: under create_graph=True the backward
+    call raises."""
 
     @staticmethod
     def forward(ctx, angles, backend=None):
@@ -41,6 +42,7 @@ class RotateMatrix(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_matrix):
+        first_order_only('RotateMatrix')
         rd = ctx.rd
         a, = ctx.saved_tensors
         g = upstream(d_matrix, a.device)
@@ -67,7 +69,7 @@ def _forward(rd, sets, a, t, c):
 class PoseVertices(torch.autograd.Function):
     """(angles, translation, center or None, backend, *vertex sets) -> one posed tensor per set.  All tensors fp32 on one device.
     Gradients go to angles, translation, a given centre and every vertex set that asks for one; an output without an upstream
-    gradient counts as zeros.  The node of the outputs (`out.grad_fn`) keeps `saved`, the [12] fp32 tensor the forward call
+    gradient counts as zeros; under create_graph=True the backward call raises (the adjoint cannot be differentiated again).  The node of the outputs (`out.grad_fn`) keeps `saved`, the [12] fp32 tensor the forward call
     wrote and the backward call reads: R row by row, then the centre that was used."""
 
     @staticmethod
@@ -86,6 +88,7 @@ class PoseVertices(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *d_out):
+        first_order_only('PoseVertices')
         rd, counts = ctx.rd, ctx.counts
         a, saved = ctx.saved_tensors[:2]
         sets = list(ctx.saved_tensors[2:2 + len(counts)])

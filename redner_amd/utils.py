@@ -18,7 +18,7 @@ CPU tensors are accepted by the CPU debugging harness only (the test-suite loads
 import torch
 
 from . import redner as _default_backend
-from ._op import named, place, ptr, scratch, upstream
+from ._op import first_order_only, named, place, ptr, scratch, upstream
 
 
 class SHReconstruct(torch.autograd.Function):
@@ -39,6 +39,7 @@ class SHReconstruct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_image):
+        first_order_only('SHReconstruct')
         rd = ctx.rd
         channels, num_coeffs, height, width, use_gpu, index = ctx.geometry
         clamp = ctx.clamp
@@ -53,7 +54,7 @@ class SHReconstruct(torch.autograd.Function):
 
 def SH_reconstruct(coeffs, res, backend=None):
     """pyredner.SH_reconstruct: the [res[0], res[1], C] fp32 image of the spherical-harmonic coefficients `coeffs` [C, N], clamped
-    at 0, on the coefficients' device.  Differentiable with respect to `coeffs` (which need not be contiguous)."""
+    at 0, on the coefficients' device.  Differentiable with respect to `coeffs` (which need not be contiguous), once: under create_graph=True the backward call raises."""
     if not isinstance(coeffs, torch.Tensor) or coeffs.dim() != 2 or coeffs.numel() == 0:
         raise ValueError('SH_reconstruct: coeffs must be a [C, N] tensor with C, N >= 1')
     if coeffs.dtype != torch.float32:

@@ -61,12 +61,18 @@ def floor_g_buffer(hg, wg, alpha, seed=11):
 
 
 def triangle_scene(tris, device):
-    """a Scene of loose triangles [T, 3, 3] (one shape, one black material); it is only ever traced, never rendered"""
-    tris = np.asarray(tris, np.float32)
+    """a Scene of loose triangles [T, 3, 3] (one shape, one black material); it is only ever traced, never rendered.  `tris`: numbers
+    or, for a caller whose vertices exist on `device` only (tests/test_native_op_calls.py), a contiguous fp32 tensor there, which
+    the scene's shape then points into: no value of it passes through the host."""
     cam = scenes.Camera(position=scenes._t([0.0, 0.0, 5.0], 'cpu'), look_at=scenes._t([0.0, 0.0, 0.0], 'cpu'),
                         up=scenes._t([0.0, 1.0, 0.0], 'cpu'), fov=scenes._t([45.0], 'cpu'), clip_near=1e-2, resolution=(4, 4))
-    shape = scenes.Shape(scenes._t(tris.reshape(-1, 3), device),
-                         scenes._t(np.arange(3 * len(tris)).reshape(-1, 3), device, torch.int32), 0)
+    if isinstance(tris, torch.Tensor):
+        assert tris.dtype == torch.float32 and tris.is_contiguous() and tris.device == torch.device(device)
+        shape = scenes.Shape(tris.reshape(-1, 3), torch.arange(3 * len(tris), dtype=torch.int32, device=device).reshape(-1, 3), 0)
+    else:
+        tris = np.asarray(tris, np.float32)
+        shape = scenes.Shape(scenes._t(tris.reshape(-1, 3), device),
+                             scenes._t(np.arange(3 * len(tris)).reshape(-1, 3), device, torch.int32), 0)
     return scenes.Scene(cam, [shape], [scenes.Material(diffuse_reflectance=scenes._t([0.0, 0.0, 0.0], device))], [])
 
 

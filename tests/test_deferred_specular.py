@@ -519,9 +519,76 @@ def _e2e_lights(ru):
                        ru.DirectionalLight(torch.tensor([-0.4, -1.0, 0.6]), torch.tensor([0.8, 0.9, 1.0]))]
 
 
-def _run_end_to_end(backend, device):
+def _cam_to_world_scene(device, resolution):
+    """the sphere over the plane seen by the same camera, given as a cam_to_world matrix (a leaf that requires a gradient): columns
+    x = normalize(cross(d, up)), y = cross(x, d), d = normalize(look_at - position), position"""
+    from redner_amd.render_pytorch import Camera
+    sc = _sphere_over_plane(device, resolution)
+    cam = sc.camera
+    pos = cam.position.detach()
+    d = (cam.look_at - pos) / (cam.look_at - pos).norm()
+    x = torch.cross(d, cam.up, dim=0)
+    x = x / x.norm()
+    matrix = torch.eye(4)
+    matrix[:3, 0], matrix[:3, 1], matrix[:3, 2], matrix[:3, 3] = x, torch.cross(x, d, dim=0), d, pos
+    sc.camera = Camera(fov=torch.tensor([40.0]), clip_near=1e-2, resolution=resolution, cam_to_world=matrix.contiguous().requires_grad_(True))
+    return sc
+
+
+def _run_cam_to_world(backend, device, monkeypatch):
+    """render_utils._eye_of takes the translation column of a cam_to_world as the eye: the image is the diffuse image + the
+    definition's lobe with that eye, and the eye's share of the gradient arrives in that column."""
+    from test_schedule_matrix import GPU_BAR
     ru = _ru()
     res, aa, seed = 32, 2, 5
+    _, lights = _e2e_lights(ru)
+    sc = _cam_to_world_scene(device, (res, res))
+    img = ru.render_deferred(sc, lights, aa_samples=aa, seed=seed, device=device, backend=backend, specular=True)
+    up = mk.upstream(img.shape).to(device)
+    (img * up).sum().backward()
+    # the look-at camera it was made from gives the same picture (the matrix is rounded to fp32: not the same bits)
+    look_at = ru.render_deferred(_sphere_over_plane(device, (res, res)), lights, aa_samples=aa, seed=seed, device=device,
+                                 backend=backend, specular=True).detach()
+    same = _worst_slice(img.detach().cpu()[None], look_at.cpu().double()[None], 'cam_to_world against look-at')
+    print('cam_to_world against the look-at camera: %.2e' % same)
+    assert same < parity_util.TOL, same
+    # = the diffuse image + the definition's lobe on render_g_buffer's own channels, the eye being the translation column
+    ch = [backend.channels.position, backend.channels.shading_normal, backend.channels.diffuse_reflectance,
+          backend.channels.specular_reflectance, backend.channels.roughness]
+    sc2 = _cam_to_world_scene(device, (res * aa, res * aa))
+    gb = ru.render_g_buffer(sc2, ch, seed=seed, device=device, backend=backend).detach().cpu().unsqueeze(0)
+    diffuse = ru.render_deferred(_cam_to_world_scene(device, (res, res)), lights, aa_samples=aa, seed=seed, device=device,
+                                 backend=backend).detach().cpu()
+    params, types = ru.pack_lights(lights, CPU)
+    lobe, _ = lobe64(gb[..., :9].double(), gb[..., 9:13].double(), sc2.camera.cam_to_world.detach()[:3, 3].double().reshape(1, 3),
+                     types, params.detach().double(), ((0, 2),), aa)
+    assert float(lobe.abs().sum()) > 0.01 * float(diffuse.abs().sum())
+    err = _worst_slice(img.detach().cpu()[None], diffuse.double()[None] + lobe, 'cam_to_world end to end')
+    print('cam_to_world end to end: %.2e' % err)
+    assert err < parity_util.TOL, err
+    # the eye's share of the gradient: with _eye_of handing out a fresh leaf of the same values, that leaf's gradient + what
+    # reaches the column through the G-buffer render is what reached the column before.  The two sides differ in the order of
+    # two or three fp32 additions and, on the GPU, by the renderer's run-to-run bar
+    whole = sc.camera.cam_to_world.grad[:3, 3].clone()
+    sc_p = _cam_to_world_scene(device, (res, res))
+    eye = sc_p.camera.cam_to_world.detach()[:3, 3].clone().requires_grad_(True)
+    with monkeypatch.context() as patch:
+        patch.setattr(ru, '_eye_of', lambda camera, rd: eye)
+        img_p = ru.render_deferred(sc_p, lights, aa_samples=aa, seed=seed, device=device, backend=backend, specular=True)
+    assert torch.equal(img_p.detach(), img.detach())
+    (img_p * up).sum().backward()
+    rest = sc_p.camera.cam_to_world.grad[:3, 3]
+    assert float(eye.grad.abs().sum()) > 0 and float(rest.abs().sum()) > 0 and float(whole.abs().sum()) > 0
+    d, n = float((eye.grad.double() + rest.double() - whole.double()).norm()), float(whole.double().norm())
+    print('the eye\'s share %s + the rest %s against the column %s: %.2e of GPU_BAR %.0e' % (eye.grad.tolist(), rest.tolist(), whole.tolist(), d / n, GPU_BAR))
+    assert d <= GPU_BAR * n, (d / n, GPU_BAR)
+    assert not torch.equal(rest, whole)
+
+
+def _run_end_to_end(backend, device, monkeypatch):
+    ru = _ru()
+    res, aa, seed = 32, 2, 5
+    _run_cam_to_world(backend, device, monkeypatch)
     sc = _sphere_over_plane(device, (res, res))
     intensity, lights = _e2e_lights(ru)
     img = ru.render_deferred(sc, lights, aa_samples=aa, seed=seed, device=device, backend=backend, specular=True)
@@ -583,13 +650,13 @@ def _run_end_to_end(backend, device):
                            backend=backend, specular=True)
 
 
-def test_end_to_end_hostsim(hostsim_backend):
-    _run_end_to_end(hostsim_backend, CPU)
+def test_end_to_end_hostsim(hostsim_backend, monkeypatch):
+    _run_end_to_end(hostsim_backend, CPU, monkeypatch)
 
 
 @pytest.mark.gpu
-def test_end_to_end_gpu(gpu_backend):
-    _run_end_to_end(gpu_backend, GPU)
+def test_end_to_end_gpu(gpu_backend, monkeypatch):
+    _run_end_to_end(gpu_backend, GPU, monkeypatch)
 
 
 # ---- 6. calling contract --------------------------------------------------------------------------------------------------------------

@@ -26,6 +26,14 @@ dev = torch.device('cpu')
 sc = scenes.two_triangles(dev, resolution=(32, 32))
 args = RenderFunction.serialize_scene(sc, 8, 1, sampler_type=redner.SamplerType.sobol, device=dev)
 img = render_sharded(3, args)
+# the adjoint cannot be differentiated again: every rank is told so before it renders or exchanges anything, and the plain pass
+# below gives the bits the test compares
+try:
+    torch.autograd.grad(img.sum(), [s.vertices for s in sc.shapes[:2]], create_graph=True, retain_graph=True)
+except RuntimeError as error:
+    assert 'DistributedRenderFunction: the native adjoint cannot be differentiated again' in str(error), error
+else:
+    raise AssertionError('create_graph=True was not refused')
 img.sum().backward()
 if dist.get_rank() == 0:
     np.savez(%(out)r, image=img.detach().numpy(), g0=sc.shapes[0].vertices.grad.numpy(), g1=sc.shapes[1].vertices.grad.numpy())

@@ -27,12 +27,23 @@ Conditions (one small case per entry point: every kernel of the op runs and one 
   D  backward(retain_graph=True), then backward(): the first gradient is the plain one, .grad ends at exactly twice it.
   E  edits in place between forward and backward: of a contiguous input the adjoint reads -> torch's saved-tensor RuntimeError;
      of the same input given as a view that is not contiguous (the op read a private copy), of an input the adjoint does not
-     read, and of an OUTPUT -> the plain gradient.
-  F  (GPU) pose_vertices with angles, translation and centre on the CPU: the plain bits, their gradients back on the CPU.
+     read, and of a differentiable OUTPUT -> the plain gradient; of a word output that the op also saved for its adjoint (the
+     visibility and occlusion words of deferred_shade: Case.saved_extras) -> the saved-tensor RuntimeError.
+  F  (GPU) the small inputs of a case (Case.small: the angles, translation and centre of pose_vertices, the light table of
+     deferred_shade, the eye and the light table of deferred_specular) on the CPU: the plain bits, their gradients back on the
+     CPU, every other gradient on the GPU.
   G  (GPU) a side stream: see _side_stream.
   H  (GPU) two host threads, each under its own stream: see test_two_host_threads_gpu.
-The harness legs run everything but F, G and H; the GPU legs run on both builds of the library."""
+  I  torch.autograd.grad(..., create_graph=True): the native adjoints cannot be differentiated again and say so
+     (redner_amd/_op.py: first_order_only) instead of handing back a first gradient that silently does not require one; a plain
+     run afterwards gives the plain bits.
+The deferred_shade cases with occluders build their occluder scene inside the call, from the case's `triangles` input, and run
+under a RDR_DEFERRED_SHADOW_CHUNK that splits their 480 texels into several chunks of the ray queue; their word outputs are
+extras.  The harness legs run everything but F, G and H; the GPU legs run on both builds of the library.
+test_render_deferred_side_stream_gpu is G for the composite render_deferred, outside the matrix."""
+import contextlib
 import itertools
+import os
 import threading
 
 import numpy as np
@@ -41,6 +52,10 @@ import torch
 
 import parity_util
 import test_deferred as t_deferred
+import test_deferred_ao as t_ao
+import test_deferred_sh as t_dsh
+import test_deferred_shadows as t_shadows
+import test_deferred_specular as t_spec
 import test_mesh_smooth as t_smooth
 import test_pose as t_pose
 import test_pyramid_loss as t_loss
@@ -59,21 +74,23 @@ INPLACE = 'modified by an inplace operation'
 # the list of conditions; CASES (below) gives every op its case(s).  envmap_sampling_tables, smooth and bound_vertices have no
 # gradient: the view and stream conditions only.
 TABLE = {
-    'generate_mipmap': 'ABCDEG',
-    'SH_reconstruct': 'ABCDEG',
+    'generate_mipmap': 'ABCDEGI',
+    'SH_reconstruct': 'ABCDEGI',
     'envmap_sampling_tables': 'AG',
-    'deferred_shade': 'ABCDEG',
-    'compute_vertex_normal': 'ABCDEG',
-    'mesh_laplacian': 'ABCDEG',
+    'deferred_shade': 'ABCDEFGHI',
+    'deferred_specular': 'ABCDEFGHI',
+    'compute_vertex_normal': 'ABCDEGI',
+    'mesh_laplacian': 'ABCDEGI',
     'smooth': 'AG',
     'bound_vertices': 'AG',
-    'gaussian_pyramid_loss': 'ABCDEGH',
-    'gen_rotate_matrix': 'ABCDEG',
-    'pose_vertices': 'ABCDEFGH',
+    'gaussian_pyramid_loss': 'ABCDEGHI',
+    'gen_rotate_matrix': 'ABCDEGI',
+    'pose_vertices': 'ABCDEFGHI',
 }
-NATIVE_OPS = ('generate_mipmap', 'SH_reconstruct', 'envmap_sampling_tables', 'deferred_shade', 'compute_vertex_normal',
-              'mesh_laplacian', 'smooth', 'bound_vertices', 'gaussian_pyramid_loss', 'gen_rotate_matrix', 'pose_vertices')
-HARNESS_CONDITIONS, GPU_CONDITIONS = 'ABCDE', 'ABCDEFG'            # (H is one test of its own)
+NATIVE_OPS = ('generate_mipmap', 'SH_reconstruct', 'envmap_sampling_tables', 'deferred_shade', 'deferred_specular',
+              'compute_vertex_normal', 'mesh_laplacian', 'smooth', 'bound_vertices', 'gaussian_pyramid_loss', 'gen_rotate_matrix',
+              'pose_vertices')
+HARNESS_CONDITIONS, GPU_CONDITIONS = 'ABCDEI', 'ABCDEFGI'          # (H is one test of its own)
 
 
 def _modules():
@@ -118,13 +135,15 @@ class Case:
     want a gradient.  call(backend, tensors) -> (differentiable outputs, other results).  cotangents: one fixed CPU tensor per
     differentiable output.  reads / unread: the inputs the adjoint reads / does not read.  subsets: condition C.  unused:
     condition B, the only outputs used.  leaf: inputs that require a gradient although nothing is differentiated (smooth).
-    definition(case, plain, backend, device): holds the plain call to the fp64 definition."""
+    saved_extras: condition E, the indices of the other results that the op saved for its adjoint.  small: condition F, the
+    inputs that may live on the host.  definition(case, plain, backend, device): holds the plain call to the fp64 definition."""
 
     def __init__(self, op, name, inputs, call, definition, diff=(), cotangents=(), reads=(), unread=(), subsets=(), unused=None,
-                 leaf=()):
+                 leaf=(), saved_extras=(), small=()):
         self.op, self.name, self.inputs, self.call, self.definition = op, name, inputs, call, definition
         self.diff, self.cotangents, self.reads, self.unread = tuple(diff), list(cotangents), tuple(reads), tuple(unread)
         self.subsets, self.unused, self.leaf = tuple(subsets), unused, tuple(leaf)
+        self.saved_extras, self.small = tuple(saved_extras), tuple(small)
 
     def __repr__(self):
         return self.name
@@ -310,7 +329,134 @@ def _deferred_case(alpha):
 
     return Case('deferred_shade', 'deferred_6x10_aa2_alpha%d' % alpha, {'g_buffer': g, 'light_params': params}, call, definition,
                 diff=('g_buffer', 'light_params'), cotangents=[weights], reads=('g_buffer', 'light_params'),
-                subsets=(('g_buffer',), ('light_params',)))
+                subsets=(('g_buffer',), ('light_params',)), small=('light_params',))
+
+
+@contextlib.contextmanager
+def _shadow_chunk(rays):
+    """csrc/deferred.h: shadow_chunk reads RDR_DEFERRED_SHADOW_CHUNK on every call (process-wide: one setter at a time)"""
+    assert 'RDR_DEFERRED_SHADOW_CHUNK' not in os.environ
+    os.environ['RDR_DEFERRED_SHADOW_CHUNK'] = str(rays)
+    try:
+        yield
+    finally:
+        del os.environ['RDR_DEFERRED_SHADOW_CHUNK']
+
+
+AO_RAYS, AO_RADIUS = 8, 0.8
+# the 480 texels of the 20 x 24 floor in at least two chunks: 256 texels of shadow rays; 8 rays x 64 texels of occlusion rays; with
+# both at once 256 serves both (two chunks of shadow rays, fifteen of 32 texels' occlusion rays)
+SHADED = {'shadowed': (True, False, 256), 'occluded': (False, True, AO_RAYS * 64), 'shadowed_occluded': (True, True, 256)}
+
+
+def _shaded_case(kind, seed=None, shared=None):
+    """deferred_shade over the floor patch of test_deferred_shadows with its BLOCKERS as the occluder scene, whose triangles are an
+    input: `call` builds the scene from t['triangles'] on every run (the adjoint needs no scene, so they are `unread`) and runs
+    the shade under the kind's chunk size.  `shared`, condition H: an occluder scene built by the caller, who also holds the
+    chunk size (the environment is the process's); `seed`: another floor."""
+    shadows, occlusion, chunk = SHADED[kind]
+    alpha = 1
+    if occlusion:                                                            # seven rows with the SH triple; normals tilted
+        g, types, params = t_ao.tilted_floor(alpha, **({} if seed is None else {'seed': seed}))
+        assert types == t_ao.ao_lights()[0] and len(types) == 7
+    else:
+        assert seed is None
+        floor = t_shadows.floor_case(alpha)
+        g, types, params = floor['g'], floor['types'], floor['params']
+    assert tuple(g.shape) == (1, t_shadows.HG, t_shadows.WG, 10) and t_shadows.HG * t_shadows.WG == 480
+    ranges = ((0, len(types)),)
+    up = mk.upstream((1, t_shadows.HG // t_shadows.AA, t_shadows.WG // t_shadows.AA, 3 + alpha))
+    triangles = torch.from_numpy(t_shadows.BLOCKERS.astype(np.float32))
+
+    def shade(rd, t, scene):
+        scenes = (scene.scene,)
+        return _modules()[1].DeferredShade.apply(t['g_buffer'], t['light_params'], tuple(types), ranges, t_shadows.AA, bool(alpha), rd,
+                                                 scenes if shadows else None, *((scenes, AO_RAYS, AO_RADIUS) if occlusion else ()))
+
+    def call(rd, t):
+        if shared is not None:
+            out = shade(rd, t, shared)
+        else:
+            device = t['g_buffer'].device
+            scene = _modules()[1].occluder_scene(t_shadows.triangle_scene(t['triangles'].contiguous(), device), device=device, backend=rd)
+            with _shadow_chunk(chunk):
+                out = shade(rd, t, scene)
+        return [out[0]], list(out[1:])
+
+    def definition(case, plain, backend, device):
+        words = list(plain['extras'])
+        assert len(words) == shadows + occlusion and all(w.dtype == torch.int32 and tuple(w.shape) == (1, 20, 24) for w in words)
+        vis = words.pop(0) if shadows else None
+        if shadows:
+            assert (t_shadows.as_words(vis) != (1 << len(types)) - 1).any()
+        if occlusion:                                                        # test_deferred_ao._run_values_and_gradients, _run_with_shadows
+            got = dict(image=plain['outs'][0], vis=vis, words=words[0], d_g=plain['grads']['g_buffer'], d_p=plain['grads']['light_params'])
+            o = t_ao._check_definition(got, g, types, params, ranges, AO_RAYS, t_shadows.AA, alpha, up, str(case))
+            assert float(o.min()) < 0.8 and float((o == 1).double().mean()) > 0.1 and float((o < 1).double().mean()) > 0.1
+            return
+        # test_deferred_shadows._run_values_and_gradients, with the mask of the device's own words
+        bits = t_shadows.as_words(vis)[0]
+        lit = np.stack([((bits >> np.uint32(b)) & 1).astype(bool) for b in range(len(types))])
+        g64, p64 = g.double().requires_grad_(True), torch.from_numpy(params).double().requires_grad_(True)
+        want = t_shadows.definition_shadowed(g64, types, p64, lit, t_shadows.AA, alpha)
+        want.backward(up.double())
+        for k, a, b in (('image', plain['outs'][0], want.detach()), ('d_g_buffer', plain['grads']['g_buffer'], g64.grad),
+                        ('d_light_params', plain['grads']['light_params'], p64.grad)):
+            worst = t_deferred._worst_slice(a, b, '%s %s' % (case, k))
+            print(case, k, '%.2e' % worst)
+            assert worst < parity_util.TOL, (case, k, worst)
+
+    name = 'deferred_%s_20x24_aa2_alpha%d' % (kind, alpha) + ('' if seed is None else '_%d' % seed)
+    inputs = {'g_buffer': g.clone(), 'light_params': torch.from_numpy(np.asarray(params, np.float32)).clone(), 'triangles': triangles}
+    return Case('deferred_shade', name, inputs, call, definition, diff=('g_buffer', 'light_params'), cotangents=[up],
+                reads=('g_buffer', 'light_params'), unread=('triangles',), subsets=(('g_buffer',), ('light_params',)),
+                saved_extras=tuple(range(shadows + occlusion)), small=('light_params',))
+
+
+SPECULAR_MASK_SEED = 41                                                      # test_deferred_specular._run_visibility
+
+
+def _specular_case(masked, seed=None):
+    """DeferredSpecular on a case of test_deferred_specular (two images, the seven mixed rows, per-image ranges): `masked`, that of
+    _run_visibility with its seeded random words as the fifth input.  `seed`, condition H: the same shapes from the generator at
+    another seed (no texel is taken off a gate: such a case is held to its own plain bits only)."""
+    name = 'grid_17x16_aa2_alpha1' if masked else 'grid_5x7_aa2_alpha1'
+    if seed is None:
+        base = t_spec._definition_case(name)
+    else:
+        n, h, w, aa, alpha, types, ranges = t_spec._shape_of(name)
+        g, mat, eye = t_spec.generate(seed, n, h, w, aa, alpha)
+        base = dict(g=g, mat=mat, eye=eye, types=types, params=t_spec.light_rows(seed + 5000, types), ranges=ranges, aa=aa, alpha=alpha)
+    n, hg, wg = base['g'].shape[:3]
+    inputs = {'g_buffer': base['g'].clone(), 'material': base['mat'].clone(), 'eye': base['eye'].clone(),
+              'light_params': torch.from_numpy(np.asarray(base['params'], np.float32)).clone()}
+    words = None
+    if masked:
+        words = torch.from_numpy(np.random.default_rng(SPECULAR_MASK_SEED).integers(-2 ** 31, 2 ** 31, (n, hg, wg), dtype=np.int64))
+        inputs['visibility'] = words.to(torch.int32)
+    up = mk.upstream((n, hg // base['aa'], wg // base['aa'], 3))
+
+    def call(rd, t):
+        return [_modules()[1].DeferredSpecular.apply(t['g_buffer'], t['material'], t['eye'], t['light_params'], tuple(base['types']),
+                                                     tuple(base['ranges']), base['aa'], bool(base['alpha']), rd, t.get('visibility'))], []
+
+    def definition(case, plain, backend, device):
+        assert seed is None
+        if masked:
+            up64, want = t_spec._reference(base, vis=words & 0xffffffff)
+            assert float((want['image'] - base['want']['image']).abs().sum()) > 0          # the mask removes light
+        else:
+            up64, want = base['up'], base['want']
+        assert torch.equal(up64, up)
+        out = {'image': plain['outs'][0], 'd_g_buffer': plain['grads']['g_buffer'], 'd_material': plain['grads']['material'],
+               'd_eye': plain['grads']['eye'], 'd_light_params': plain['grads']['light_params']}
+        t_spec._assert_parity(out, want, str(case))
+
+    diff = ('g_buffer', 'material', 'eye', 'light_params')
+    label = 'specular_%s%dx%d_aa%d_alpha%d' % ('masked_' if masked else '', hg // base['aa'], wg // base['aa'], base['aa'], base['alpha'])
+    return Case('deferred_specular', label + ('' if seed is None else '_%d' % seed), inputs, call, definition, diff=diff,
+                cotangents=[up], reads=tuple(inputs), subsets=tuple((n,) for n in diff) + (('material', 'eye'),),
+                small=('eye', 'light_params'))
 
 
 BOX, GRID = 'box4', 'grid7x9'               # closed, irregular, 98 vertices: more than one workgroup; open, 63 vertices
@@ -483,7 +629,8 @@ def _pose_case(given, seed=2801):
     reads = tuple(n for n in inputs if n != 'translation')
     subsets = (('translation',), ('v1',)) + ((('center',),) if given else ())
     return Case('pose_vertices', 'pose_%s_%d' % ('given' if given else 'own', seed), inputs, call, definition, diff=diff, cotangents=weights,
-                reads=reads, unread=('translation',), subsets=subsets, unused=(1,))
+                reads=reads, unread=('translation',), subsets=subsets, unused=(1,),
+                small=tuple(n for n in ('angles', 'translation', 'center') if n in inputs))
 
 
 # op -> its cases, name -> how the case is made.  A case is built (inputs, and for the mip pyramid the fp64 reference it shares
@@ -492,7 +639,12 @@ CASES = {
     'generate_mipmap': {'mipmap_5x7x3': lambda: _mip_case((5, 7, 3)), 'mipmap_70x66x3': lambda: _mip_case((70, 66, 3))},
     'SH_reconstruct': {'sh_3x16_9x33': _sh_case},
     'envmap_sampling_tables': {'envmap_tables_6x70': _envmap_case},
-    'deferred_shade': {'deferred_6x10_aa2_alpha0': lambda: _deferred_case(0), 'deferred_6x10_aa2_alpha1': lambda: _deferred_case(1)},
+    'deferred_shade': {'deferred_6x10_aa2_alpha0': lambda: _deferred_case(0), 'deferred_6x10_aa2_alpha1': lambda: _deferred_case(1),
+                       'deferred_shadowed_20x24_aa2_alpha1': lambda: _shaded_case('shadowed'),
+                       'deferred_occluded_20x24_aa2_alpha1': lambda: _shaded_case('occluded'),
+                       'deferred_shadowed_occluded_20x24_aa2_alpha1': lambda: _shaded_case('shadowed_occluded')},
+    'deferred_specular': {'specular_5x7_aa2_alpha1': lambda: _specular_case(False),
+                          'specular_masked_17x16_aa2_alpha1': lambda: _specular_case(True)},
     'compute_vertex_normal': {'vertex_normal_max': lambda: _normal_case('max'), 'vertex_normal_cotangent': lambda: _normal_case('cotangent')},
     'mesh_laplacian': {'mesh_laplacian_reciprocal': lambda: _laplacian_case('reciprocal'),
                        'mesh_laplacian_uniform': lambda: _laplacian_case('uniform'),
@@ -527,11 +679,18 @@ def test_table_is_complete():
     assert sorted(TABLE) == sorted(NATIVE_OPS) == sorted(CASES)
     for op in NATIVE_OPS:
         assert callable(getattr(redner_amd, op, None) or getattr(render_utils, op)), op
-        assert CASES[op] and all(_case(name).op == op for name in CASES[op]) and set(TABLE[op]) <= set('ABCDEFGH'), op
+        assert CASES[op] and all(_case(name).op == op for name in CASES[op]) and set(TABLE[op]) <= set('ABCDEFGHI'), op
         assert all(('B' in TABLE[op]) == bool(_case(name).diff) for name in CASES[op]), op                # an op with a gradient gets the gradient conditions
-    assert set(''.join(TABLE.values())) == set('ABCDEFGH') == set(CONDITIONS) | {'H'}
-    assert set(HARNESS_CONDITIONS) | set('FGH') == set(GPU_CONDITIONS) | {'H'} == set('ABCDEFGH')
+        assert ('I' in TABLE[op]) == ('B' in TABLE[op]), op                                              # ... and refuses a second differentiation
+        assert all(('F' in TABLE[op]) == bool(_case(name).small) for name in CASES[op]), op                # ... F, where inputs may live on the host
+    assert 'deferred_specular' in TABLE and 'I' in HARNESS_CONDITIONS and 'I' in GPU_CONDITIONS
+    assert set(''.join(TABLE.values())) == set('ABCDEFGHI') == set(CONDITIONS) | {'H'}
+    assert set(HARNESS_CONDITIONS) | set('FGH') == set(GPU_CONDITIONS) | {'H'} == set('ABCDEFGHI')
     assert len(set(ALL_CASES)) == len(ALL_CASES)
+    # every existing case keeps no word output; the occluder cases save theirs; the small inputs are inputs
+    for case in map(_case, ALL_CASES):
+        assert bool(case.saved_extras) == ('shadowed' in case.name or 'occluded' in case.name), case
+        assert set(case.small) <= set(case.diff), case
     # condition E names every input of every differentiable op on one side or the other
     for case in map(_case, ALL_CASES):
         if case.diff:
@@ -667,6 +826,15 @@ def _edits(case, backend, device):
     for name in case.unread:
         got = _run(case, backend, device, between=lambda t, o, name=name: _edit(t[name]))
         _same(got, plain, '%s: %s edited between forward and backward' % (case, name), keys=('grads',))
+    # a word output that the op saved for its adjoint is the caller's tensor too: the same check must fire
+    for k in case.saved_extras:
+        tensors = _make(case, device)
+        outs, extras = case.call(backend, tensors)
+        assert not extras[k].requires_grad and extras[k].dtype == torch.int32
+        with torch.no_grad():
+            _edit(extras[k])
+        with pytest.raises(RuntimeError, match=INPLACE):
+            torch.autograd.backward(outs, _cotangents(case, device))
     # no op keeps its result by alias
     for k in range(len(case.cotangents)):
         got = _run(case, backend, device, between=lambda t, o, k=k: _edit(o[k]))
@@ -676,13 +844,15 @@ def _edits(case, backend, device):
 
 # ---- F. small parameters on the CPU -----------------------------------------------------------------------------------------------
 def _small_on_cpu(case, backend, device):
-    assert device.type == 'cuda' and case.op == 'pose_vertices'
+    assert device.type == 'cuda' and case.small
     plain = _plain(case, backend, device)
-    small = [n for n in ('angles', 'translation', 'center') if n in case.inputs]
+    small = [n for n in case.small if n in case.inputs]
+    assert small == list(case.small) and set(small) < set(case.diff)
     tensors = _make(case, device, place={n: _on_cpu for n in small})
+    assert all(tensors[n].device.type == 'cpu' for n in small)
     outs, extras = case.call(backend, tensors)
     torch.autograd.backward(outs, _cotangents(case, device))
-    assert all(tensors[n].grad.device.type == 'cpu' for n in small) and tensors['v0'].grad.device.type == 'cuda'
+    assert all(tensors[n].grad.device.type == ('cpu' if n in small else 'cuda') for n in case.diff)
     _same(_snapshot(case, tensors, outs, extras), plain, '%s: %s on the CPU' % (case, ', '.join(small)))
 
 
@@ -690,6 +860,15 @@ def _small_on_cpu(case, backend, device):
 def _poisoned(t):
     """A buffer of t's shape that no kernel may read yet: NaN (an index tensor: zeros, which stay in range)."""
     return torch.full_like(t, float('nan')) if t.is_floating_point() else torch.zeros_like(t)
+
+
+def _late(device):
+    """The producer chain of _side_stream, on the current stream: 20 additions over 2^26 floats -> a 0-dim tensor that is 0, but
+    not before the chain has run."""
+    big = torch.zeros(1 << 26, device=device)
+    for _ in range(20):
+        big = big + 1.0
+    return big[:1].sum() - 20.0
 
 
 def _side_stream(case, backend, device):
@@ -707,11 +886,7 @@ def _side_stream(case, backend, device):
     side = torch.cuda.Stream(device=device)
     torch.cuda.synchronize(device)
     with torch.cuda.stream(side):
-        big = torch.zeros(1 << 26, device=device)
-        for _ in range(20):
-            big = big + 1.0
-        late = big[:1].sum() - 20.0                                             # == 0, but ordered after the chain
-        del big
+        late = _late(device)                                                    # == 0, but ordered after the chain
         tensors = _make(case, device, place={name: (lambda x, d, name=name: torch.add(staged[name], late.to(staged[name].dtype),
                                                                                       out=buffers[name])) for name in case.inputs})
         cotangents = [torch.add(w, late, out=b) for w, b in zip(weights, weight_buffers)]
@@ -727,7 +902,22 @@ def _side_stream(case, backend, device):
     torch.cuda.empty_cache()                                                    # (the producer's 256 MB blocks)
 
 
-CONDITIONS = {'A': _views, 'B': _upstream, 'C': _wanted, 'D': _twice, 'E': _edits, 'F': _small_on_cpu, 'G': _side_stream}
+# ---- I. a second differentiation --------------------------------------------------------------------------------------------------
+def _second_order(case, backend, device):
+    """Autograd runs `backward` in grad mode exactly under create_graph=True; the kernels of an adjoint record nothing, so the
+    first gradient would come back not requiring a gradient and a loss built on it would drop that term without a word."""
+    plain = _plain(case, backend, device)
+    tensors = _make(case, device)
+    outs, _ = case.call(backend, tensors)
+    with pytest.raises(RuntimeError, match='cannot be differentiated again'):
+        torch.autograd.grad(outs, [tensors[n] for n in case.diff], _cotangents(case, device), create_graph=True)
+    assert all(tensors[n].grad is None for n in case.diff)
+    # nothing was left half-done: the same case, plain
+    _same(_run(case, backend, device), plain, '%s: a plain run after the refused one' % case)
+
+
+CONDITIONS = {'A': _views, 'B': _upstream, 'C': _wanted, 'D': _twice, 'E': _edits, 'F': _small_on_cpu, 'G': _side_stream,
+              'I': _second_order}
 
 
 @pytest.mark.parametrize('name,letter', _pairs(HARNESS_CONDITIONS))
@@ -745,14 +935,29 @@ def test_calls_gpu(gpu_backend, name, letter):
 @pytest.mark.gpu
 def test_two_host_threads_gpu(gpu_backend):
     """rdr_set_stream is state of the calling host thread: two Python threads, each under its own side stream, started
-    together, each run gaussian_pyramid_loss and pose_vertices forward and backward ten times on their own inputs and get the
-    plain bits of those inputs every time.  (One process, two threads.)  What this covers is the FORWARD launches: autograd
-    runs the backward node of a device tensor on its one worker thread of that device (under the forward call's stream), not on
-    the Python thread that called backward(), so the backward launches of both threads come from the same host thread."""
-    assert set('H') <= set(TABLE['gaussian_pyramid_loss']) & set(TABLE['pose_vertices'])
-    work = [[_loss_case(2900 + 10 * k), _pose_case(bool(k), 2950 + 10 * k)] for k in range(2)]
+    together, each run gaussian_pyramid_loss, pose_vertices, the shadowed and occluded deferred_shade and the masked
+    deferred_specular forward and backward ten times on their own inputs and get the plain bits of those inputs every time.
+    (One process, two threads.)  The occluder scene is built once, by the main thread, and traced by both threads under their
+    two streams -- the walk kernels and their counters (hip/runtime.hip: persistent_counter) with two customers at once; the
+    chunk size is set once around both, the environment being the process's.  What this covers is the FORWARD launches:
+    autograd runs the backward node of a device tensor on its one worker thread of that device (under the forward call's
+    stream), not on the Python thread that called backward(), so the backward launches of both threads come from the same host
+    thread."""
+    assert all('H' in TABLE[op] for op in ('gaussian_pyramid_loss', 'pose_vertices', 'deferred_shade', 'deferred_specular'))
+    blockers = t_shadows.occluder(gpu_backend, t_shadows.BLOCKERS, GPU)
+    work = [[_loss_case(2900 + 10 * k), _pose_case(bool(k), 2950 + 10 * k), _shaded_case('shadowed_occluded', 3000 + 10 * k, blockers),
+             _specular_case(True, 3050 + 10 * k)] for k in range(2)]
+    with _shadow_chunk(SHADED['shadowed_occluded'][2]):
+        _two_host_threads(gpu_backend, work)
+
+
+def _two_host_threads(gpu_backend, work):
     plains = [[_plain(case, gpu_backend, GPU) for case in cases] for cases in work]
-    assert not torch.equal(plains[0][0]['outs'][0], plains[1][0]['outs'][0])
+    for item in range(len(work[0])):
+        assert not torch.equal(plains[0][item]['outs'][0], plains[1][item]['outs'][0]), item
+    for k in range(2):                                                         # both occluder paths and the mask did something
+        vis, occlusion = (t_shadows.as_words(w) for w in plains[k][2]['extras'])
+        assert (vis != 127).any() and (occlusion != (1 << AO_RAYS) - 1).any()
     staged = [[({n: x.clone().to(GPU) for n, x in case.inputs.items()}, _cotangents(case, GPU)) for case in cases] for cases in work]
     torch.cuda.synchronize(GPU)
     start, failures = threading.Barrier(2), []
@@ -779,3 +984,72 @@ def test_two_host_threads_gpu(gpu_backend):
     for t in threads:
         t.join()
     assert not failures, failures
+
+
+# ---- G for the composite: render_deferred with everything on, on a side stream ------------------------------------------------------
+@pytest.mark.gpu
+def test_render_deferred_side_stream_gpu(gpu_backend):
+    """render_deferred(alpha, shadows, ambient occlusion, specular) of test_deferred_specular's sphere over a plane at 16 x 16,
+    forward and backward under `with torch.cuda.stream(side)`: the G-buffer render, the occluder scene, the shadow and
+    occlusion rays, both deferred kernels and their adjoints, and RenderFunction's adjoint, all behind _side_stream's producer
+    chain -- the sphere's vertices, both materials' specular reflectance and roughness and the point light's intensity are
+    written into NaN buffers as x + late on that stream; the camera position stays on the host.  Held to the same call on the
+    default stream: the image and the gradient of the light's intensity (which passes through the deferred kernels only) bit for
+    bit; the gradients that pass through RenderFunction (vertices, materials, camera position), which are summed with fp64
+    atomics and are not bitwise reproducible from run to run, to test_schedule_matrix.GPU_BAR relative L2.  As for
+    _side_stream: a correct library cannot fail this; a wrong one can pass by timing."""
+    from redner_amd.render_pytorch import Texture
+    from test_schedule_matrix import GPU_BAR
+    ru = _modules()[1]
+    res, aa, seed = 16, 2, 5
+    written = ('vertices', 'ks0', 'roughness0', 'ks1', 'roughness1', 'intensity')
+
+    def run(side):
+        sc = t_spec._sphere_over_plane(GPU, (res, res))
+        on = lambda x: torch.tensor(x, device=GPU)
+        staged = {'vertices': sc.shapes[0].vertices.detach().clone(), 'intensity': on([12.0, 11.0, 10.0])}
+        for m in range(2):
+            staged['ks%d' % m] = sc.materials[m].specular_reflectance.mipmap[0].detach().clone()
+            staged['roughness%d' % m] = sc.materials[m].roughness.mipmap[0].detach().clone()
+        assert sorted(staged) == sorted(written) and sc.camera.position.device.type == 'cpu' and sc.camera.position.requires_grad
+        # (the lights' other tensors on the device beforehand: a copy from the host would make the host wait for the stream)
+        rest = [on([1.5, 3.0, -1.0]), on([-0.4, -1.0, 0.6]), on([0.8, 0.9, 1.0]), on([0.1, 0.12, 0.14]),
+                torch.from_numpy(t_dsh.sh_coefficients(3)).to(GPU)]
+        buffers, weights = {name: _poisoned(x) for name, x in staged.items()}, mk.upstream((res, res, 4)).to(GPU)
+        buffers['upstream'] = _poisoned(weights)
+        torch.cuda.synchronize(GPU)
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            late = _late(GPU) if side is not None else torch.zeros((), device=GPU)
+            leaf = {name: torch.add(x, late, out=buffers[name]).requires_grad_(True) for name, x in staged.items()}
+            sc.shapes[0].vertices = leaf['vertices']
+            for m in range(2):
+                sc.materials[m].specular_reflectance, sc.materials[m].roughness = Texture(leaf['ks%d' % m]), Texture(leaf['roughness%d' % m])
+            lights = [ru.PointLight(rest[0], leaf['intensity']), ru.DirectionalLight(rest[1], rest[2]), ru.AmbientLight(rest[3]),
+                      ru.SHLight(rest[4])]
+            img = ru.render_deferred(sc, lights, alpha=True, shadows=True, ambient_occlusion=4, ao_radius=1.0, specular=True,
+                                     aa_samples=aa, seed=seed, device=GPU, backend=gpu_backend)
+            img.backward(torch.add(weights, late, out=buffers['upstream']))
+            total = img.detach().double().sum()                                 # a consumer on the same stream
+        if side is not None:
+            side.synchronize()
+        else:
+            torch.cuda.synchronize(GPU)
+        out = {'image': _keep(img), 'camera position': _keep(sc.camera.position.grad)}
+        out.update({name: _keep(t.grad) for name, t in leaf.items()})
+        assert float(total) == float(out['image'].double().sum())
+        return out
+
+    want = run(None)
+    assert tuple(want['image'].shape) == (res, res, 4)
+    for name, t in want.items():
+        assert t is not None and bool(torch.isfinite(t).all()) and bool(t.any()), name
+    got = run(torch.cuda.Stream(device=GPU))
+    torch.cuda.empty_cache()                                                    # (the producer's 256 MB blocks)
+    for name in ('image', 'intensity'):
+        assert torch.equal(got[name], want[name]), (name, 'differs from the default stream in %d of %d elements'
+                                                    % (int((got[name] != want[name]).sum()), want[name].numel()))
+    for name in ('vertices', 'ks0', 'roughness0', 'ks1', 'roughness1', 'camera position'):
+        assert got[name] is not None and got[name].device.type == 'cpu', name
+        d, n = float((got[name].double() - want[name].double()).norm()), float(want[name].double().norm())
+        print('render_deferred on a side stream, d_%s: %.2e of GPU_BAR %.0e' % (name, d / n, GPU_BAR))
+        assert d <= GPU_BAR * n + 1e-30, (name, d / n)

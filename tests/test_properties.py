@@ -65,3 +65,25 @@ def test_backward_is_linear_hostsim(hostsim_backend, name, res, spp):
 def test_backward_is_linear_gpu(gpu_backend, name, res, spp):
     build, mb = CASES[name]
     _linearity(gpu_backend, torch.device('cuda:0'), build, res, spp, mb, 2e-6)
+
+
+def test_render_function_refuses_create_graph_hostsim(hostsim_backend):
+    """The adjoint render cannot be differentiated again: under create_graph=True RenderFunction.backward says so (before it
+    launches anything) instead of returning a first gradient that silently does not require one; the same graph then gives the
+    plain gradient."""
+    device = torch.device('cpu')
+    build, mb = CASES['two_triangles']
+    sc = build(device, resolution=(48, 48))
+    args = RenderFunction.serialize_scene(sc, 4, mb, sampler_type=hostsim_backend.SamplerType.sobol, device=device, backend=hostsim_backend)
+    img = RenderFunction.apply(5, *args)
+    ins = _inputs(sc)
+    g = torch.ones_like(img)
+    with pytest.raises(RuntimeError, match='RenderFunction: the native adjoint cannot be differentiated again'):
+        torch.autograd.grad(img, ins, grad_outputs=g, create_graph=True, retain_graph=True)
+    first = torch.autograd.grad(img, ins, grad_outputs=g)
+    assert all(not t.requires_grad and bool(t.any()) for t in first)
+    sc2 = build(device, resolution=(48, 48))
+    again = RenderFunction.apply(5, *RenderFunction.serialize_scene(sc2, 4, mb, sampler_type=hostsim_backend.SamplerType.sobol,
+                                                                    device=device, backend=hostsim_backend))
+    for a, b in zip(first, torch.autograd.grad(again, _inputs(sc2), grad_outputs=g)):
+        assert torch.equal(a, b)

@@ -100,6 +100,14 @@ def run(fn):
     sc.camera.position.requires_grad_(True)
     args = RenderFunction.serialize_scene(sc, 8, 4, sampler_type=redner.SamplerType.sobol, device=dev)
     img = fn(args)
+    # the adjoint render cannot be differentiated again: refused before anything is rendered or exchanged (the two collectives
+    # counted below stay two), and the plain pass that follows gives the gradients the test compares
+    try:
+        torch.autograd.grad(img.sum(), [s.vertices for s in sc.shapes if s.vertices.requires_grad], create_graph=True, retain_graph=True)
+    except RuntimeError as error:
+        assert 'RenderFunction: the native adjoint cannot be differentiated again' in str(error), error
+    else:
+        raise AssertionError('create_graph=True was not refused')
     img.sum().backward()
     torch.cuda.synchronize()
     out = {'image': img.detach().cpu().numpy(), 'light': sc.area_lights[0].intensity.grad.cpu().numpy(),
