@@ -8,6 +8,8 @@
 #include "deferred.h"
 #include "deferred_specular_abi.h"
 #include "deferred_specular.h"
+#include "deferred_quad_abi.h"
+#include "deferred_quad.h"
 #include "mipmap.h"
 #include "vertex_normal.h"
 #include "mesh_smooth.h"
@@ -220,6 +222,23 @@ int rdr_deferred_specular_backward(const rdr_deferred_desc *desc, const float *g
         OnDevice on(desc->gpu_index);
         rdr::dfs::specular_backward(*desc, g_buffer, material, eye, light_params, d_image, d_g_buffer, d_material, d_eye,
                                     d_light_params);
+    });
+}
+
+int rdr_deferred_quad(const rdr_deferred_desc *desc, const float *g_buffer, const float *quads, float *image) {
+    return status([&] {
+        if (!desc) throw std::runtime_error("rdr_deferred_quad: a description is required");
+        OnDevice on(desc->gpu_index);
+        rdr::dfq::quad(*desc, g_buffer, quads, image);
+    });
+}
+
+int rdr_deferred_quad_backward(const rdr_deferred_desc *desc, const float *g_buffer, const float *quads, const float *d_image,
+                               float *d_g_buffer, float *d_quads) {
+    return status([&] {
+        if (!desc) throw std::runtime_error("rdr_deferred_quad_backward: a description is required");
+        OnDevice on(desc->gpu_index);
+        rdr::dfq::quad_backward(*desc, g_buffer, quads, d_image, d_g_buffer, d_quads);
     });
 }
 

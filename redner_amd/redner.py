@@ -510,6 +510,24 @@ def deferred_specular_backward(g_buffer, material, eye, light_params, d_image, d
           on=(use_gpu, gpu_index))
 
 
+def deferred_quad(g_buffer, quads, image, num_images, height, width, aa_samples, alpha, two_sided, image_quad_ranges, use_gpu,
+                  gpu_index):
+    """Not in the reference: rdr_deferred_quad (csrc/deferred_quad_abi.h).  g_buffer [N, H * aa, W * aa, 9 + alpha], quads [Q, 16]
+    (corners q0..q3, radiance, one unused float), image [N, H, W, 3]: float_ptr; two_sided: Q flags (0 one-sided, 1 two-sided);
+    image_quad_ranges: N (begin, end) pairs into the rows of `quads`."""
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, two_sided, image_quad_ranges, use_gpu, gpu_index)
+    _call(_capi.lib(), 'deferred_quad', 'rdr_deferred_quad', C.byref(d), _ptr(g_buffer), _ptr(quads), _ptr(image),
+          on=(use_gpu, gpu_index))
+
+
+def deferred_quad_backward(g_buffer, quads, d_image, d_g_buffer, d_quads, num_images, height, width, aa_samples, alpha, two_sided,
+                           image_quad_ranges, use_gpu, gpu_index):
+    """Not in the reference: rdr_deferred_quad_backward; writes every element of d_g_buffer and d_quads."""
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, two_sided, image_quad_ranges, use_gpu, gpu_index)
+    _call(_capi.lib(), 'deferred_quad_backward', 'rdr_deferred_quad_backward', C.byref(d), _ptr(g_buffer), _ptr(quads),
+          _ptr(d_image), _ptr(d_g_buffer), _ptr(d_quads), on=(use_gpu, gpu_index))
+
+
 def mip_num_levels(height, width):
     """Not in the reference's module: rdr_mip_num_levels, min(ceil(log2(max(height, width))) + 1, 8)."""
     return int(_capi.lib().rdr_mip_num_levels(int(height), int(width)))

@@ -69,6 +69,26 @@ shadowing, Schlick Fresnel; one-sided -- under the point, spot and directional l
 
 so a PointLight gives the path tracer's direct specular term for a point source.  Ambient lights and SHLights cast no highlight.
 Every clamp and the roughness floor pass half the gradient at the tie; the conditions and the visibility bits are constants.
+
+Quad lights (`QuadLight(vertices, intensity)`, `quad_light(position, look_at, size, intensity)`, `deferred_quad(g_buffer, lights)`;
+not in the reference, whose deferred lights have no area): a rectangular emitter of uniform radiance L, the deferred counterpart
+of the path tracer's `AreaLight` on a quad, as ONE native kernel and its adjoint (`rdr_deferred_quad`, csrc/deferred_quad.h).  The
+diffuse irradiance of a polygon has a closed form -- Lambert's contour integral, clipped to the texel's horizon -- so the light
+is exact and free of noise.  Per texel, with the corners q0..q3 in perimeter order (the emitting side is that of
+cross(q1 - q0, q3 - q0)):
+
+    nh = n / |n|,  r_i = q_i - p,  h_i = nh.r_i                       nothing unless n != 0
+    S = sum over the edges r_i -> r_i+1, each clipped to h > 0 (an end below is replaced by the crossing point x), of
+        edge(A, B) = atan2(|c|, A.B) * (c.nh) / |c|,  c = B x A,      + edge(exit, entry) when the horizon cut the quad
+    F = max(S, 0) / 2  (two_sided: |S| / 2)
+    L * (a / pi) * F
+
+F / pi is the view factor; a quad that fills the hemisphere gives L * a.  The normal is normalised (the point light uses it as
+stored).  Gradients reach p, n, a, the four corners and L; max(S, 0) passes half the gradient at S == 0, |S| passes sign(S), the
+conditions are constants.  A QuadLight never enters the ten-float light table: `render_deferred` shades the table lights as before
+and adds `deferred_quad` of the quads.  NOT done: quad lights are not shadowed by `shadows=True` (and do
+not count towards its 32 rows), are not dimmed by ambient occlusion and cast no specular highlight; the emitter's own surface,
+where it is in the G-buffer, is shaded like any other surface.
 """
 import random
 from typing import List, Optional, Union
@@ -166,6 +186,110 @@ class SHLight(DeferredLight):
         return c
 
 
+_QUAD_FLOATS = 16          # csrc/deferred_quad.h: corners 12, radiance 3, one unused
+
+
+class QuadLight(DeferredLight):
+    """A rectangular area light of uniform radiance (not in the reference's deferred pass): `vertices` [4, 3], the corners in
+    perimeter order, `intensity` [3], the radiance.  It emits on the side of cross(v1 - v0, v3 - v0), or on both with
+    `two_sided`; the quad is expected to be planar and convex.  Every texel gets the exact diffuse irradiance of the part above
+    its horizon (the module docstring has the formula).  It is shaded by `deferred_quad` (`render_deferred` does so for the
+    QuadLights in its list) and never enters the light table: it casts no shadow, is not dimmed by ambient occlusion and casts
+    no specular highlight."""
+    light_type = None
+
+    def __init__(self, vertices: torch.Tensor, intensity: torch.Tensor, two_sided: bool = False):
+        self.vertices, self.intensity, self.two_sided = vertices, intensity, bool(two_sided)
+        self._checked()
+
+    def _checked(self):
+        v, i = torch.as_tensor(self.vertices), torch.as_tensor(self.intensity)
+        if tuple(v.shape) != (4, 3):
+            raise RuntimeError('QuadLight: vertices must be [4, 3] (the corners in perimeter order), got %s' % (tuple(v.shape),))
+        if i.numel() != 3:
+            raise RuntimeError('QuadLight: intensity must be [3] (the radiance), got %s' % (tuple(i.shape),))
+        return v, i
+
+    def render(self, position: torch.Tensor, normal: torch.Tensor, albedo: torch.Tensor):
+        """This light alone on explicit position / normal / albedo images ([..., 3] each, broadcast against each other),
+        through the same native kernel as render_deferred."""
+        position, normal, albedo = torch.broadcast_tensors(position, normal, albedo)
+        shape = position.shape
+        if len(shape) < 1 or shape[-1] != 3:
+            raise RuntimeError('QuadLight.render: position, normal and albedo must be [..., 3]')
+        g = torch.cat([position, normal, albedo], dim=-1).to(torch.float32)
+        g = g.reshape(1, 1, -1, 9) if g.dim() < 3 else g.reshape((-1,) + tuple(g.shape[-3:]))
+        return deferred_quad(g, [self], alpha=False, aa_samples=1).reshape(shape)
+
+
+def quad_light(position: torch.Tensor, look_at: torch.Tensor, size: torch.Tensor, intensity: torch.Tensor,
+               two_sided: bool = False):
+    """The QuadLight that coincides with the emitter of the reference's `generate_quad_light(position, look_at, size, intensity)`:
+    a rectangle of `size` [2] centred at `position`, emitting towards `look_at`, in the same in-plane frame.  With
+    d = normalize(look_at - position), a = 1 / (1 + d.z) and b = -d.x d.y a, the frame is x = (1 - d.x d.x a, b, -d.x),
+    y = (b, 1 - d.y d.y a, -d.y) (at the pole d.z < -1 + 1e-6: x = (0, -1, 0), y = (-1, 0, 0)), so x cross y = d, and the
+    corners are position -+ x size[0] / 2 -+ y size[1] / 2 in the order (-, -), (+, -), (+, +), (-, +): the same four points as
+    the emitter's, whose triangles are (0, 1, 3) and (1, 2, 3) of these.  Torch operations: autograd carries the gradients of the
+    corners to `position`, `look_at` and `size`."""
+    position, look_at, size = (torch.as_tensor(t) for t in (position, look_at, size))
+    d = look_at - position
+    d = d / torch.norm(d)
+    if float(d[2]) < -1 + 1e-6:                # (which branch is taken is a constant of the gradient)
+        x, y = d.new_tensor([0.0, -1.0, 0.0]), d.new_tensor([-1.0, 0.0, 0.0])
+    else:
+        a = 1 / (1 + d[2])
+        b = -d[0] * d[1] * a
+        x, y = torch.stack([1 - d[0] * d[0] * a, b, -d[0]]), torch.stack([b, 1 - d[1] * d[1] * a, -d[1]])
+    ex, ey = x * size[0] * 0.5, y * size[1] * 0.5
+    vertices = torch.stack([position - ex - ey, position + ex - ey, position + ex + ey, position - ex + ey])
+    return QuadLight(vertices, intensity, two_sided=two_sided)
+
+
+def _split_quads(lights):
+    """a list of lights, or one list per image -> (the same without its QuadLights, the QuadLights in the same shape or None when
+    there is none)"""
+    if len(lights) > 0 and isinstance(lights[0], (list, tuple)):
+        quads = [[light for light in lgts if isinstance(light, QuadLight)] for lgts in lights]
+        if not any(quads):
+            return lights, None
+        return [[light for light in lgts if not isinstance(light, QuadLight)] for lgts in lights], quads
+    quads = [light for light in lights if isinstance(light, QuadLight)]
+    if not quads:
+        return lights, None
+    return [light for light in lights if not isinstance(light, QuadLight)], quads
+
+
+def pack_quads(lights, device):
+    """[Q, 16] fp32 table on `device` (layout: csrc/deferred_quad.h) + the Q two_sided flags.  One cat over the lights' tensors:
+    autograd routes the table's gradient back to them."""
+    pieces, flags = [], []
+    unused = torch.zeros(1, dtype=torch.float32, device=device)
+    for light in lights:
+        if not isinstance(light, QuadLight):
+            raise RuntimeError('deferred_quad: %r is not a QuadLight (the other lights are shaded by deferred_shade)' % (light,))
+        v, i = light._checked()
+        pieces += [v.to(device=device, dtype=torch.float32).reshape(-1), i.to(device=device, dtype=torch.float32).reshape(-1), unused]
+        flags.append(int(light.two_sided))
+    if not pieces:
+        return torch.zeros(0, _QUAD_FLOATS, dtype=torch.float32, device=device), flags
+    return torch.cat(pieces).reshape(len(flags), _QUAD_FLOATS), flags
+
+
+def _quad_table(lights, n, device):
+    """one list of QuadLights shared by the n images, or n lists -> (quads [Q, 16], the Q flags, the n row ranges)"""
+    if len(lights) > 0 and isinstance(lights[0], (list, tuple)):
+        if len(lights) != n:
+            raise RuntimeError('deferred_quad: %d light lists for %d images' % (len(lights), n))
+        flat, ranges = [], []
+        for lgts in lights:
+            ranges.append((len(flat), len(flat) + len(lgts)))
+            flat.extend(lgts)
+    else:
+        flat, ranges = list(lights), [(0, len(lights))] * n
+    quads, flags = pack_quads(flat, device)
+    return quads, flags, ranges
+
+
 def _num_rows(lights):
     """rows of the light table that a list of lights takes: one per light, three per SHLight"""
     return sum(getattr(light, 'num_rows', 1) for light in lights)
@@ -176,7 +300,7 @@ def _check_lights(lights):
     for light in lights:
         if isinstance(light, (list, tuple)):
             _check_lights(light)
-        elif isinstance(light, SHLight):
+        elif isinstance(light, (SHLight, QuadLight)):
             light._checked()
 
 
@@ -187,6 +311,9 @@ def pack_lights(lights, device):
     pieces, types = [], []
     zeros = {n: torch.zeros(n, dtype=torch.float32, device=device) for n in (1, 3, 6, 9)}
     for light in lights:
+        if isinstance(light, QuadLight):
+            raise RuntimeError('render_deferred: a QuadLight has no row in the light table of deferred_shade and deferred_specular: '
+                               'shade it with deferred_quad (render_deferred does so for the QuadLights in its list)')
         if not isinstance(light, DeferredLight) or light.light_type is None:
             raise RuntimeError('render_deferred: %r is not a deferred light' % (light,))
         if isinstance(light, SHLight):
@@ -482,6 +609,69 @@ def deferred_specular(g_buffer, material, lights, eye, alpha=False, aa_samples=1
                                   visibility)
 
 
+class DeferredQuad(torch.autograd.Function):
+    """apply(g_buffer [N, H * aa, W * aa, 9 + alpha], quads [Q, 16], two_sided, image_quad_ranges, aa_samples, alpha, backend)
+    -> [N, H, W, 3]: the light of the quads of its image (module docstring) on every texel, averaged over each aa x aa block.
+    `quads`: a row is the corners q0..q3, the radiance and one unused float; `two_sided`: Q flags, 0 or 1;
+    `image_quad_ranges`: N (begin, end) pairs into the rows.  One native launch forward, one (+ the fold of the quad gradients)
+    backward; gradients reach the nine channels of the G-buffer and the table.  The gradients cannot be differentiated again:
+    under create_graph=True the backward call raises."""
+
+    @staticmethod
+    def forward(ctx, g_buffer, quads, two_sided, image_quad_ranges, aa_samples, alpha, backend=None):
+        rd = backend or _default_backend
+        two_sided = tuple(int(t) for t in two_sided)
+        image_quad_ranges = tuple((int(b), int(e)) for b, e in image_quad_ranges)
+        aa_samples, alpha = int(aa_samples), bool(alpha)
+        channels = 9 + int(alpha)
+        if g_buffer.dim() != 4 or g_buffer.shape[3] != channels:
+            raise RuntimeError('DeferredQuad: the G-buffer must be [N, H * aa, W * aa, %d], got %s'
+                               % (channels, tuple(g_buffer.shape)))
+        n, hg, wg = int(g_buffer.shape[0]), int(g_buffer.shape[1]), int(g_buffer.shape[2])
+        if aa_samples < 1 or hg % aa_samples != 0 or wg % aa_samples != 0 or n == 0 or hg == 0 or wg == 0:
+            raise RuntimeError('DeferredQuad: a G-buffer of %d x %d x %d does not divide into aa_samples = %d blocks'
+                               % (n, hg, wg, aa_samples))
+        if tuple(quads.shape) != (len(two_sided), _QUAD_FLOATS):
+            raise RuntimeError('DeferredQuad: quads must be [%d, %d], got %s' % (len(two_sided), _QUAD_FLOATS, tuple(quads.shape)))
+        if len(image_quad_ranges) != n:
+            raise RuntimeError('DeferredQuad: %d quad ranges for %d images' % (len(image_quad_ranges), n))
+        if g_buffer.dtype != torch.float32 or quads.dtype != torch.float32:
+            raise RuntimeError('DeferredQuad: fp32 tensors only')
+        device = g_buffer.device
+        use_gpu, index = place(device)
+        g = _aligned(g_buffer.detach(), alpha)
+        table = quads.detach().to(device).contiguous()
+        h, w = hg // aa_samples, wg // aa_samples
+        image = torch.empty(n, h, w, 3, dtype=torch.float32, device=device)
+        geometry = (n, h, w, aa_samples, alpha, two_sided, image_quad_ranges, use_gpu, index)
+        ctx.rd, ctx.geometry, ctx.quads_device = rd, geometry, quads.device
+        rd.deferred_quad(ptr(rd, g), ptr(rd, table), ptr(rd, image), *geometry)
+        ctx.save_for_backward(g, table)
+        return image
+
+    @staticmethod
+    def backward(ctx, grad_img):
+        first_order_only('DeferredQuad')
+        rd, geometry = ctx.rd, ctx.geometry
+        g, table = ctx.saved_tensors
+        grad_img = upstream(grad_img, g.device)
+        assert torch.isfinite(grad_img).all()
+        d_g, d_table = torch.empty_like(g), torch.empty_like(table)
+        rd.deferred_quad_backward(ptr(rd, g), ptr(rd, table), ptr(rd, grad_img), ptr(rd, d_g), ptr(rd, d_table), *geometry)
+        return d_g, d_table.to(ctx.quads_device), None, None, None, None, None
+
+
+def deferred_quad(g_buffer, lights, alpha=False, aa_samples=1, backend=None):
+    """The light of QuadLights on a stack of G-buffers [N, H * aa, W * aa, 9 + alpha] -> [N, H, W, 3], to be added to the colour
+    channels of `deferred_shade`'s image.  `lights`: one list of QuadLight shared by the N images, or N lists (an empty one is
+    fine).  The lights are exact, unshadowed area emitters (the module docstring has the formula and what is left out);
+    gradients reach position, normal and albedo, and the corners and radiance of every QuadLight -- through `quad_light`, its
+    position, look_at and size."""
+    n = int(g_buffer.shape[0])
+    quads, flags, ranges = _quad_table(lights, n, g_buffer.device)
+    return DeferredQuad.apply(g_buffer, quads, tuple(flags), tuple(ranges), aa_samples, alpha, backend)
+
+
 def _default_device(device):
     if device is not None:
         return device
@@ -528,6 +718,14 @@ def _eye_of(camera, backend):
     return torch.as_tensor(camera.position).reshape(3)
 
 
+def _add_quads(images, g_buffer, quad_lights, alpha, aa_samples, backend):
+    """images + deferred_quad of the QuadLights on the same G-buffer; the alpha channel is left as it is"""
+    light = deferred_quad(g_buffer, quad_lights, alpha=alpha, aa_samples=aa_samples, backend=backend)
+    if alpha:
+        light = torch.cat([light, torch.zeros_like(light[..., :1])], dim=-1)
+    return images + light
+
+
 def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = False, aa_samples: int = 2, seed=None,
                     sample_pixel_center: bool = False, use_primary_edge_sampling: bool = True,
                     device: Optional[torch.device] = None, backend=None, shadows: bool = False, ambient_occlusion: int = 0,
@@ -553,13 +751,19 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
     docstring has the formula) is added to the colour channels; with `shadows`, a blocked light casts no highlight.  The eye is
     the camera's position (the translation column of a `cam_to_world`), so an orthographic camera raises.  Gradients reach
     `specular_reflectance`, `roughness`, the geometry, the lights and the camera position.  Ambient occlusion leaves the
-    highlights alone.  False: the same launches and the same bits as without the argument."""
+    highlights alone.  False: the same launches and the same bits as without the argument.
+    QuadLights (redner_amd extension) may stand in `lights` among the others, in a shared list or in per-scene lists: the others
+    are shaded exactly as without them, the quads by `deferred_quad` on the same G-buffer, and the sum is returned (alpha is the
+    diffuse pass's).  Quad lights are NOT shadowed by `shadows` and do not count towards its 32 rows, are NOT dimmed by
+    `ambient_occlusion` and cast NO specular highlight; the emitter's own surface, where the scene holds it, is shaded like any
+    other surface.  Without a QuadLight in `lights`: the same launches and the same bits as before there were any."""
     backend = backend or _default_backend
     device = _default_device(device)
     aa_samples = int(aa_samples)
     if aa_samples < 1:
         raise RuntimeError('render_deferred: aa_samples must be at least 1')
     _check_lights(lights)
+    lights, quad_lights = _split_quads(lights)
     channels = [backend.channels.position, backend.channels.shading_normal, backend.channels.diffuse_reflectance]
     if alpha:
         channels.append(backend.channels.alpha)
@@ -579,6 +783,8 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
         images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend,
                                 occluders=built if shadows else None, ambient_occlusion=ambient_occlusion, ao_radius=ao_radius,
                                 ao_occluders=built if ambient_occlusion else None)
+        if quad_lights is not None:
+            images = _add_quads(images, g_buffer, quad_lights, alpha, aa_samples, backend)
         return images[0] if single else images
     # the diffuse part exactly as above on its own channels (asking for the words when there are shadows), then the lobe
     diffuse_channels = 9 + int(bool(alpha))
@@ -593,6 +799,8 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
     if alpha:
         highlights = torch.cat([highlights, torch.zeros_like(highlights[..., :1])], dim=-1)
     images = images + highlights
+    if quad_lights is not None:
+        images = _add_quads(images, g, quad_lights, alpha, aa_samples, backend)
     return images[0] if single else images
 
 
