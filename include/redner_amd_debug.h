@@ -20,6 +20,27 @@ extern "C" {
  * back untouched. */
 int rdr_debug_lane_park(int num_lanes, const uint8_t *active, const double *in, double *out, int32_t *columns);
 
+/* Test hook: rdr_scene_trace with every input of the launch plan (csrc/trace_plan.h) in the caller's hands, so that one process
+ * can run every traversal kernel.  `tuning` as in rdr_render_options (null: the defaults); `coherent` as the render stages pass
+ * it; trace_hybrid: -1 keeps the process's setting (RDR_TRACE_HYBRID), 0 / 1 override it -- the one plan input that is no field
+ * of rdr_tuning; device_count (may be null): an int in the Scene's memory, the queue then holds min(*device_count, num_rays)
+ * rays and the slots of `hits` from there on are not written.  Counting kernels are selected by rdr_trace_stats_enable, as for
+ * rdr_scene_trace.  rays / hits: the Scene's memory, num_rays records (0 .. 2^24).  rdr_debug_scene_trace_plan with the same
+ * num_rays, any_hit, coherent, counting and tuning reports the launch this makes when trace_hybrid is -1; with an override
+ * only the refilling kernel's int-entry tier changes (trace_plan.h: stack 16 with the hybrid stack, else 32 up to a need of
+ * 32 and 40 beyond), which the caller derives (tests/test_trace_tiers.py). */
+int rdr_debug_scene_trace(const rdr_scene *scene, const float *rays, int32_t *hits, int num_rays, int any_hit, int coherent,
+                          const rdr_tuning *tuning, int trace_hybrid, const int32_t *device_count);
+
+/* Test hook, host arithmetic in every build: how many stack entries each ray uses.  The host builder (csrc/bvh.cpp) builds the
+ * hierarchy of the Scene's meshes afresh -- what rdr_debug_bvh_check compares the kernels' build with -- and every ray of
+ * host_rays (HOST memory, num_rays records of 8 floats) walks it with rt::traverse (wide = 0) or rt::traverse_wide (wide = 1)
+ * over a stack pre-filled with a value no walk pushes; max_entries[i] = the highest stack index ray i wrote, plus one (0: it
+ * pushed nothing, or the slot is dead).  max_entries[num_rays .. num_rays + 3] = {node records, stack_need, 4-wide records,
+ * wide_stack_need} of that hierarchy: num_rays + 4 ints in all. */
+int rdr_debug_trace_occupancy(const rdr_scene *scene, const float *host_rays, int num_rays, int any_hit, int wide,
+                              int32_t *max_entries);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,8 @@ HEADERS = {
     },
     'redner_amd_debug.h': {                  # test hooks that came after redner_amd.h was fixed
         'rdr_debug_lane_park': (_i, [_i, _p, _p, _p, _p]),
+        'rdr_debug_scene_trace': (_i, [_p, _p, _p, _i, _i, _i, C.POINTER(Tuning), _i, _p]),
+        'rdr_debug_trace_occupancy': (_i, [_p, _p, _i, _i, _i, _p]),
     },
 }
 

@@ -67,7 +67,7 @@ struct Builder {
                 Box bins[kMaxBins]; int cnt[kMaxBins] = {0};
                 float scale = kBins / ext;
                 for (int i = first; i < first + count; ++i) {
-                    int bi = std::min(kBins - 1, std::max(0, (int)((prims[i].c[axis] - cb.lo[axis]) * scale)));
+                    int bi = sah_bin(prims[i].c[axis], cb.lo[axis], scale, kBins);
                     bins[bi].grow(prims[i].lo, prims[i].hi); cnt[bi]++;
                 }
                 float ra[kMaxBins]; int rc[kMaxBins];
@@ -92,7 +92,7 @@ struct Builder {
             // (stable: the order of a leaf's triangles is then a function of the input order alone, and equals the device
             //  builder's ballot-ranked partition, bvh_gpu.cpp)
             Prim *it = std::stable_partition(prims + first, prims + first + count, [&](const Prim &p) {
-                int bi = std::min(kBins - 1, std::max(0, (int)((p.c[best_axis] - lo) * scale)));
+                int bi = sah_bin(p.c[best_axis], lo, scale, kBins);
                 return bi <= best_bin;
             });
             mid = (int)(it - prims);

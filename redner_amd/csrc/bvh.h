@@ -52,6 +52,15 @@ struct BvhD {              // device/host view
 
 struct Counters { unsigned long long nodes, tris; };
 
+// The SAH bin of a centroid c on an axis whose centroids start at `lo`, scale = bins / extent (both builders, bvh.cpp and
+// bvh_gpu.cpp).  An extent below 64 / FLT_MAX makes `scale` infinite and the product inf or NaN; converting those to int is
+// undefined, the host gave bin 0 and the device the last bin, and the two hierarchies differed (hits never did: raytri.h).
+// Here every input has one answer: NaN and everything <= 0 the first bin, everything beyond the last bin the last.
+RT_HD inline int sah_bin(float c, float lo, float scale, int bins) {
+    const float f = (c - lo) * scale;
+    return f >= (float)(bins - 1) ? bins - 1 : (f > 0.f ? (int)f : 0);
+}
+
 // Ray queue records exchanged between the shading stages and the traversal kernels (HBM, dense by
 // queue slot).  A dead slot has tmax < 0 and always reports a miss.
 struct alignas(16) RayRec { float ox, oy, oz, tmin, dx, dy, dz, tmax; };   // 32 B

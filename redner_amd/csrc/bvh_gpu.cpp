@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(64) decide_kernel(const WorkItem *work, int nw
             for (int j = lane; j < w.count; j += 64) {
                 const float *b = boxes + 6 * (size_t)perm[w.first + j];
                 const float c = 0.5f * (b[a] + b[3 + a]);
-                const int bi = min(bins - 1, max(0, (int)((c - clo[a]) * scale)));
+                const int bi = sah_bin(c, clo[a], scale, bins);
                 for (int k = 0; k < 3; ++k) { atomicMin(&s_lo[wave][a][bi][k], enc(b[k])); atomicMax(&s_hi[wave][a][bi][k], enc(b[3 + k])); }
                 atomicAdd(&s_cnt[wave][a][bi], 1);
             }
@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(64) apply_kernel(const WorkItem *work, int nwo
             if (d.kind == 1) {
                 const float *b = boxes + 6 * (size_t)p;
                 const float c = 0.5f * (b[d.axis] + b[3 + d.axis]);
-                left = min(bins - 1, max(0, (int)((c - d.lo) * d.scale))) <= d.bin;
+                left = sah_bin(c, d.lo, d.scale, bins) <= d.bin;
             } else left = w.first + j < d.mid;
         }
         const unsigned long long ml = __ballot(valid && left), mr = __ballot(valid && !left);

@@ -16,6 +16,7 @@
 #include "sh_envmap.h"
 #include "pyramid_loss.h"
 #include "pose.h"
+#include <algorithm>
 #include <cstdio>
 #include "scene.h"
 #include <cstring>
@@ -603,6 +604,64 @@ int rdr_debug_scene_trace_plan(const rdr_scene *scene, int num_rays, int any_hit
     return status([&] {
         if (!scene) throw std::runtime_error("rdr_debug_scene_trace_plan: bad arguments");
         write_trace_plan(exec::trace_facts(reinterpret_cast<const rdr::Scene *>(scene)->bvh), num_rays, any_hit, coherent, counting, tuning, out);
+    });
+}
+
+/* Test hook: exec::trace() with every plan input chosen by the caller (include/redner_amd_debug.h). */
+int rdr_debug_scene_trace(const rdr_scene *scene, const float *rays, int32_t *hits, int num_rays, int any_hit, int coherent,
+                          const rdr_tuning *tuning, int trace_hybrid, const int32_t *device_count) {
+    return status([&] {
+        const rdr::Scene &s = scene_of(scene, "rdr_debug_scene_trace");
+        if (num_rays < 0 || num_rays > kDebugMaxItems) throw std::runtime_error("rdr_debug_scene_trace: num_rays outside [0, 2^24]");
+        if (num_rays > 0 && (!rays || !hits)) throw std::runtime_error("rdr_debug_scene_trace: an array is missing");
+        if (trace_hybrid < -1 || trace_hybrid > 1) throw std::runtime_error("rdr_debug_scene_trace: trace_hybrid is -1, 0 or 1");
+        OnDevice on(s);
+        rdr::Tuning t = rdr::resolve_tuning(tuning);
+        if (trace_hybrid >= 0) t.trace_hybrid = trace_hybrid != 0;
+        const rdr::TuningScope scope(t);
+        exec::trace(s.bvh, reinterpret_cast<const rt::RayRec *>(rays), reinterpret_cast<rt::HitRec *>(hits),
+                    device_count ? exec::Count(device_count, num_rays) : exec::Count(num_rays), any_hit != 0, coherent != 0);
+        exec::sync();
+    });
+}
+
+/* Test hook: stack entries per ray on the host builder's hierarchy of the Scene's meshes (include/redner_amd_debug.h). */
+int rdr_debug_trace_occupancy(const rdr_scene *scene, const float *host_rays, int num_rays, int any_hit, int wide, int32_t *max_entries) {
+    return status([&] {
+        const rdr::Scene &s = scene_of(scene, "rdr_debug_trace_occupancy");
+        if (num_rays < 0 || num_rays > kDebugMaxItems) throw std::runtime_error("rdr_debug_trace_occupancy: num_rays outside [0, 2^24]");
+        if (!max_entries || (num_rays > 0 && !host_rays)) throw std::runtime_error("rdr_debug_trace_occupancy: an array is missing");
+        std::vector<rt::MeshView> meshes(s.shapes.size());
+        for (size_t i = 0; i < s.shapes.size(); ++i) meshes[i] = rt::MeshView{s.h_vertices[i].data(), s.h_indices[i].data(), s.shapes[i].num_triangles};
+        const rt::BvhHost h = rt::build_bvh(meshes);
+        rt::BvhD view{};
+        view.nodes = h.nodes.data(); view.tris = h.tris.data(); view.ids = h.ids.data();
+        view.num_nodes = (int)h.nodes.size(); view.num_tris = (int)h.ids.size() / 2; view.stack_need = h.depth + 2;
+        view.wide = h.wide.empty() ? nullptr : h.wide.data(); view.num_wide = (int)h.wide.size(); view.wide_stack_need = h.wide_stack_need;
+        // No walk pushes this value: binary entries are node indices, wide entries links of children that were hit (bvh.h).  A binary
+        // walk pushes at most once per level and a wide one at most three times, so the columns below cannot be overrun.
+        constexpr int kNeverPushed = rt::kEmptyLink;
+        std::vector<int> stack((size_t)4 * (wide ? view.wide_stack_need : view.stack_need) + 64);
+        const rt::RayRec *rays = reinterpret_cast<const rt::RayRec *>(host_rays);
+        for (int i = 0; i < num_rays; ++i) {
+            const rt::RayRec &r = rays[i];
+            max_entries[i] = 0;
+            if (r.tmax < 0.f) continue;
+            std::fill(stack.begin(), stack.end(), kNeverPushed);
+            const float o[3] = {r.ox, r.oy, r.oz}, d[3] = {r.dx, r.dy, r.dz};
+            if (wide) {
+                if (any_hit) rt::traverse_wide<true>(view, o, d, r.tmin, r.tmax, stack.data(), 1, nullptr);
+                else rt::traverse_wide<false>(view, o, d, r.tmin, r.tmax, stack.data(), 1, nullptr);
+            } else {
+                if (any_hit) rt::traverse<true>(view, o, d, r.tmin, r.tmax, stack.data(), 1);
+                else rt::traverse<false>(view, o, d, r.tmin, r.tmax, stack.data(), 1);
+            }
+            int top = (int)stack.size();
+            while (top > 0 && stack[top - 1] == kNeverPushed) --top;
+            max_entries[i] = top;
+        }
+        const int32_t facts[4] = {view.num_nodes, view.stack_need, view.num_wide, view.wide_stack_need};
+        std::memcpy(max_entries + num_rays, facts, sizeof(facts));
     });
 }
 

@@ -421,3 +421,22 @@ def living_room_standin(device, resolution=(1024, 1024), envmap_variant=False):
 
 def living_room_standin_envmap(device, resolution=(1024, 1024)):
     return living_room_standin(device, resolution, envmap_variant=True)
+
+
+CHAIN_AXIS = np.array([1.0, 0.3, 0.2]) / np.linalg.norm([1.0, 0.3, 0.2])
+
+
+def chain(device, ratio, n, resolution=(16, 16), scale=1.0):
+    """A hierarchy of a chosen depth (tests/test_trace_tiers.py): one shape of n separate triangles, triangle i a copy of the first
+    shrunk by ratio ** -i towards the origin along CHAIN_AXIS, so that every triangle's box straddles that axis and the SAH builder
+    peels the large ones off one per level.  fp32 arithmetic throughout; `scale` multiplies every vertex (the refit test).  A diffuse
+    material, no light.  Not a BASELINE configuration."""
+    f = np.float32
+    s = np.array([float(ratio) ** -i for i in range(n)]).astype(f)[:, None, None]
+    off = np.array([[-0.05, -0.2, -0.1], [0.05, 0.2, -0.1], [0.0, 0.0, 0.25]], f)[None]
+    v = (s * np.array([1.0, 0.3, 0.2], f)[None, None] + s * off).astype(f)
+    v = (v * f(scale)).astype(f).reshape(3 * n, 3)
+    cam = Camera(position=_t([0.0, 0.0, -5.0], 'cpu'), look_at=_t([0.0, 0.0, 0.0], 'cpu'),
+                 up=_t([0.0, 1.0, 0.0], 'cpu'), fov=_t([45.0], 'cpu'), clip_near=1e-2, resolution=resolution)
+    shape = Shape(torch.from_numpy(v).to(device), torch.arange(3 * n, dtype=torch.int32).reshape(n, 3).to(device), 0)
+    return Scene(cam, [shape], [Material(diffuse_reflectance=_t([0.5, 0.5, 0.5], device))], [])

@@ -82,7 +82,7 @@ DECLARED = {
     'redner_amd_image.h': ['rdr_pyramid_loss', 'rdr_pyramid_loss_backward', 'rdr_pyramid_loss_plan', 'rdr_pyramid_loss_scratch'],
     'redner_amd_pose.h': ['rdr_pose_plan', 'rdr_pose_scratch', 'rdr_pose_vertices', 'rdr_pose_vertices_backward',
                           'rdr_rotate_matrix', 'rdr_rotate_matrix_backward'],
-    'redner_amd_debug.h': ['rdr_debug_lane_park'],
+    'redner_amd_debug.h': ['rdr_debug_lane_park', 'rdr_debug_scene_trace', 'rdr_debug_trace_occupancy'],
 }
 
 
