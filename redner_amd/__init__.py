@@ -10,7 +10,9 @@
                                  specular highlights (`specular=True`, `deferred_specular`): the specular lobe of the path
                                  tracer's BSDF under the point, spot and directional lights, one native kernel and its adjoint
                                  rectangular area lights (`QuadLight`, `quad_light`, `deferred_quad`): the exact diffuse
-                                 irradiance of a quad emitter, clipped to the horizon, one native kernel and its adjoint
+                                 irradiance of a quad emitter, clipped to the horizon, one native kernel and its adjoint;
+                                 softly shadowed by `quad_shadow_rays=K` (`deferred_quad(occluders=..., shadow_rays=K)`,
+                                 `DeferredQuadShadowed`): K any-hit rays per texel and quad weight a visibility factor
     redner_amd.texture           mip-mapped Texture / EnvironmentMap and generate_mipmap on the native pyramid kernels:
                                  `from redner_amd import Texture, EnvironmentMap, generate_mipmap`; envmap_sampling_tables:
                                  the sampling tables of an environment map by one native call
@@ -32,7 +34,7 @@
 import sys
 
 _RENDER_UTILS = ('DeferredLight', 'AmbientLight', 'PointLight', 'DirectionalLight', 'SpotLight', 'SHLight', 'DeferredShade',
-                 'deferred_shade', 'DeferredSpecular', 'deferred_specular', 'QuadLight', 'quad_light', 'DeferredQuad',
+                 'deferred_shade', 'DeferredSpecular', 'deferred_specular', 'QuadLight', 'quad_light', 'DeferredQuad', 'DeferredQuadShadowed',
                  'deferred_quad', 'occluder_scene', 'render_deferred', 'render_generic', 'render_g_buffer', 'render_albedo',
                  'render_pathtracing')
 _TEXTURE = ('Texture', 'EnvironmentMap', 'generate_mipmap', 'MipPyramid', 'envmap_sampling_tables')

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in include/redner_amd.h and its companion headers (redner_amd_mesh.h, _image.h, _pose.h, _debug.h;
-csrc/deferred_specular_abi.h, csrc/deferred_quad_abi.h).
+csrc/deferred_specular_abi.h, csrc/deferred_quad_abi.h, csrc/deferred_quad_shadow_abi.h).
 
 The shared library is the product: `redner_amd/lib/libredner_amd.so`, built by
 `__graft_entry__.build()` (hipcc, gfx950).  If it is missing the import fails loudly -- there is
@@ -236,6 +236,10 @@ CSRC_HEADERS = {
     'deferred_quad_abi.h': {                 # rectangular area lights in deferred shading (csrc/deferred_quad.h)
         'rdr_deferred_quad': (_i, [C.POINTER(DeferredDesc), _p, _p, _p]),
         'rdr_deferred_quad_backward': (_i, [C.POINTER(DeferredDesc)] + [_p] * 5),
+    },
+    'deferred_quad_shadow_abi.h': {          # soft shadows of the quad lights (csrc/deferred_quad_shadow.h)
+        'rdr_deferred_quad_shadowed': (_i, [C.POINTER(DeferredDesc), _p, _p, _i, _p, _p]),
+        'rdr_deferred_quad_shadowed_backward': (_i, [C.POINTER(DeferredDesc)] + [_p] * 6),
     },
 }
 

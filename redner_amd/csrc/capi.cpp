@@ -10,6 +10,8 @@
 #include "deferred_specular.h"
 #include "deferred_quad_abi.h"
 #include "deferred_quad.h"
+#include "deferred_quad_shadow_abi.h"
+#include "deferred_quad_shadow.h"
 #include "mipmap.h"
 #include "vertex_normal.h"
 #include "mesh_smooth.h"
@@ -240,6 +242,24 @@ int rdr_deferred_quad_backward(const rdr_deferred_desc *desc, const float *g_buf
         if (!desc) throw std::runtime_error("rdr_deferred_quad_backward: a description is required");
         OnDevice on(desc->gpu_index);
         rdr::dfq::quad_backward(*desc, g_buffer, quads, d_image, d_g_buffer, d_quads);
+    });
+}
+
+int rdr_deferred_quad_shadowed(const rdr_deferred_desc *desc, const float *g_buffer, const float *quads, int shadow_rays,
+                               float *factors, float *image) {
+    return status([&] {
+        if (!desc) throw std::runtime_error("rdr_deferred_quad_shadowed: a description is required");
+        OnDevice on(desc->gpu_index);
+        rdr::dfq::quad_shadowed(*desc, g_buffer, quads, shadow_rays, factors, image);
+    });
+}
+
+int rdr_deferred_quad_shadowed_backward(const rdr_deferred_desc *desc, const float *g_buffer, const float *quads,
+                                        const float *factors, const float *d_image, float *d_g_buffer, float *d_quads) {
+    return status([&] {
+        if (!desc) throw std::runtime_error("rdr_deferred_quad_shadowed_backward: a description is required");
+        OnDevice on(desc->gpu_index);
+        rdr::dfq::quad_shadowed_backward(*desc, g_buffer, quads, factors, d_image, d_g_buffer, d_quads);
     });
 }
 

@@ -36,6 +36,9 @@
 // A gated texel or edge adds exactly 0 to every gradient.  Gradients go to p, n, a, the twelve corner floats and L.  The only
 // fp64 is the per-quad partial sums of the adjoint.
 //
+// SOFT SHADOWS (deferred_quad_shadow.h): the SHADOWED instantiations of the bodies and kernels below multiply F by a visibility
+// factor per (quad, texel) that a shadow pass stored; the plain ones are untouched by it.
+//
 // The per-texel bodies are shared by the kernels at the end of this header (one lane per OUTPUT pixel) and by the plain loops of
 // the CPU debugging harness.  They walk the four edges with constant indices, carrying S, the exit and entry points and the
 // edges that made them: no per-lane array is indexed by a computed value.
@@ -179,9 +182,12 @@ RDR_DEV_FN void unwalk_edge(int i, const float *A, const float *B, float hA, flo
 // What quad `quad` (sixteen floats) adds to texel t with frame f.  !ADJOINT: rgb += its light.  ADJOINT, for the texel's upstream
 // gradient w[3]: dt += the texel's gradient and, when PARAMS, part[15] += the quad's.  (The two passes of the adjoint kernel each
 // use one half; the other is dead code there.)
-template <bool ADJOINT, bool PARAMS>
+// SHADOWED (here, in the three bodies below and in the kernels): V, the visibility factor of this (quad, texel) pair that the
+// shadow pass stored (deferred_quad_shadow.h), multiplies F: F V stands where F stands, and dF is multiplied by V.  V is a
+// constant of the adjoint.  The plain instantiation never looks at V and is the code it was before there were soft shadows.
+template <bool ADJOINT, bool PARAMS, bool SHADOWED = false>
 RDR_DEV_FN void quad_light(const float *quad, bool two_sided, const Texel &t, const Frame &f, const float *w, float *rgb, Texel &dt,
-                           double *part) {
+                           double *part, float V = 1.f) {
     float r0[3], r1[3], r2[3], r3[3];
     for (int k = 0; k < 3; ++k) {
         r0[k] = quad[k] - t.p[k]; r1[k] = quad[3 + k] - t.p[k]; r2[k] = quad[6 + k] - t.p[k]; r3[k] = quad[9 + k] - t.p[k];
@@ -197,7 +203,8 @@ RDR_DEV_FN void quad_light(const float *quad, bool two_sided, const Texel &t, co
     const bool crossed = wk.exit_edge >= 0 || wk.entry_edge >= 0;
     if (crossed) wk.S += edge_form(wk.ex, wk.en, f.nh);
     const float S = wk.S;
-    const float F = (two_sided ? fabsf(S) : fmaxf(S, 0.f)) / 2.f;
+    const float F0 = (two_sided ? fabsf(S) : fmaxf(S, 0.f)) / 2.f;
+    const float F = SHADOWED ? F0 * V : F0;
     const float *L = quad + kRadiance;
     if (!ADJOINT) {
         for (int k = 0; k < 3; ++k) rgb[k] += (L[k] * (t.a[k] / kPi)) * F;
@@ -210,6 +217,7 @@ RDR_DEV_FN void quad_light(const float *quad, bool two_sided, const Texel &t, co
         dt.a[k] += ((w[k] * L[k]) * F) / kPi;
         if (PARAMS) part[kRadiance + k] += (double)((w[k] * (t.a[k] / kPi)) * F);
     }
+    if (SHADOWED) dF = dF * V;
     const float pass = two_sided ? (S > 0.f ? 1.f : (S < 0.f ? -1.f : 0.f)) : step_half(S);
     const float dS = (dF / 2.f) * pass;
     if (dS == 0.f) return;
@@ -230,9 +238,17 @@ RDR_DEV_FN void quad_light(const float *quad, bool two_sided, const Texel &t, co
     }
 }
 
+// Where the factor of pair `pair` of an image and texel (tx, ty) of pixel (x, y) stands among the image's factors.
+RDR_DEV_FN size_t factor_at(const View &v, int pair, int y, int x, int ty, int tx) {
+    const size_t hg = (size_t)v.height * v.aa, wg = (size_t)v.width * v.aa;
+    return ((size_t)pair * hg + (size_t)y * v.aa + ty) * wg + (size_t)x * v.aa + tx;
+}
+
 // One OUTPUT pixel of image n: the light of the quads [lb, le) on its aa x aa texels, averaged, three floats.
-template <int C>
-RDR_DEV_FN void quad_pixel(const View &v, int n, int pix, int lb, int le, float *image) {
+// `factors` (SHADOWED): the image's first pair, [le - lb][height * aa][width * aa]; V is fetched before the edge walk and held as
+// one scalar.
+template <int C, bool SHADOWED = false>
+RDR_DEV_FN void quad_pixel(const View &v, int n, int pix, int lb, int le, float *image, const float *factors = nullptr) {
     const int y = pix / v.width, x = pix - y * v.width;
     float acc[3] = {0.f, 0.f, 0.f};
     for (int ty = 0; ty < v.aa; ++ty) {
@@ -244,8 +260,10 @@ RDR_DEV_FN void quad_pixel(const View &v, int n, int pix, int lb, int le, float 
             Frame f;
             if (!frame_at(t, f)) continue;
             float rgb[3] = {0.f, 0.f, 0.f};
-            for (int l = lb; l < le; ++l)
-                quad_light<false, false>(v.params + (size_t)l * kQuadFloats, v.type[l] != 0, t, f, nullptr, rgb, dt, nullptr);
+            for (int l = lb; l < le; ++l) {
+                const float V = SHADOWED ? factors[factor_at(v, l - lb, y, x, ty, tx)] : 1.f;
+                quad_light<false, false, SHADOWED>(v.params + (size_t)l * kQuadFloats, v.type[l] != 0, t, f, nullptr, rgb, dt, nullptr, V);
+            }
             for (int k = 0; k < 3; ++k) acc[k] += rgb[k];
         }
     }
@@ -262,8 +280,9 @@ RDR_DEV_FN void load_upstream(const View &v, int n, int pix, const float *d_imag
 
 // Adjoint, pass 1: the gradient of every texel of one output pixel (each texel belongs to exactly one pixel: plain stores).
 // All nine channels are written; the alpha channel is 0.
-template <int C>
-RDR_DEV_FN void quad_adjoint_texels(const View &v, int n, int pix, int lb, int le, const float *d_image, float *d_g) {
+template <int C, bool SHADOWED = false>
+RDR_DEV_FN void quad_adjoint_texels(const View &v, int n, int pix, int lb, int le, const float *d_image, float *d_g,
+                                    const float *factors = nullptr) {
     const int y = pix / v.width, x = pix - y * v.width;
     float w[3];
     load_upstream(v, n, pix, d_image, w);
@@ -277,8 +296,10 @@ RDR_DEV_FN void quad_adjoint_texels(const View &v, int n, int pix, int lb, int l
             for (int k = 0; k < 3; ++k) dt.p[k] = dt.n[k] = dt.a[k] = 0.f;
             Frame f;
             if (frame_at(t, f))
-                for (int l = lb; l < le; ++l)
-                    quad_light<true, false>(v.params + (size_t)l * kQuadFloats, v.type[l] != 0, t, f, w, nullptr, dt, nullptr);
+                for (int l = lb; l < le; ++l) {
+                    const float V = SHADOWED ? factors[factor_at(v, l - lb, y, x, ty, tx)] : 1.f;
+                    quad_light<true, false, SHADOWED>(v.params + (size_t)l * kQuadFloats, v.type[l] != 0, t, f, w, nullptr, dt, nullptr, V);
+                }
             float *o = drow + tx * C;
             if (C == 10) {
                 F2 *q = reinterpret_cast<F2 *>(o);
@@ -292,8 +313,10 @@ RDR_DEV_FN void quad_adjoint_texels(const View &v, int n, int pix, int lb, int l
 }
 
 // Adjoint, pass 2: what one output pixel adds to the fifteen gradients of quad l.
-template <int C>
-RDR_DEV_FN void quad_adjoint_params(const View &v, int n, int pix, int l, const float *d_image, double *part) {
+// (`factors`, SHADOWED: the factors of quad l's own pair, [height * aa][width * aa])
+template <int C, bool SHADOWED = false>
+RDR_DEV_FN void quad_adjoint_params(const View &v, int n, int pix, int l, const float *d_image, double *part,
+                                    const float *factors = nullptr) {
     const int y = pix / v.width, x = pix - y * v.width;
     float w[3];
     load_upstream(v, n, pix, d_image, w);
@@ -308,47 +331,60 @@ RDR_DEV_FN void quad_adjoint_params(const View &v, int n, int pix, int l, const 
             for (int k = 0; k < 3; ++k) dt.p[k] = dt.n[k] = dt.a[k] = 0.f;
             Frame f;
             if (!frame_at(t, f)) continue;
-            quad_light<true, true>(quad, two_sided, t, f, w, nullptr, dt, part);
+            const float V = SHADOWED ? factors[factor_at(v, 0, y, x, ty, tx)] : 1.f;
+            quad_light<true, true, SHADOWED>(quad, two_sided, t, f, w, nullptr, dt, part, V);
         }
     }
+}
+
+// The factors of image n's first pair: pair_base[n] is the sum of the earlier images' range lengths.
+RDR_DEV_FN const float *image_factors(const View &v, const float *factors, const int *pair_base, int n) {
+    return factors + (size_t)pair_base[n] * ((size_t)v.height * v.aa * (size_t)v.width * v.aa);
 }
 
 #if !defined(RDR_HOSTSIM)
 // ---- gfx950 kernels --------------------------------------------------------------------------------------------------------
 // grid = (blocks per image, N): the quad range of a block is uniform, so the table is read through scalar loads.
-template <int C>
+// SHADOWED: `factors` [pairs][height * aa][width * aa] and `pair_base` [N], the first pair of each image; the plain instantiations
+// look at neither.
+template <int C, bool SHADOWED>
 __global__ void __launch_bounds__(256) deferred_quad_kernel(const float *__restrict__ g, const float *__restrict__ quads,
                                                             const int *__restrict__ type, const int *__restrict__ range, int height,
-                                                            int width, int aa, float *__restrict__ image) {
+                                                            int width, int aa, float *__restrict__ image,
+                                                            const float *__restrict__ factors, const int *__restrict__ pair_base) {
     const View v{g, quads, type, range, height, width, aa};
     const int n = blockIdx.y, pixels = v.height * v.width;
     const int lb = v.range[2 * n], le = v.range[2 * n + 1];
+    const float *fi = SHADOWED ? image_factors(v, factors, pair_base, n) : nullptr;
     for (int pix = blockIdx.x * 256 + threadIdx.x; pix < pixels; pix += gridDim.x * 256)
-        quad_pixel<C>(v, n, pix, lb, le, image);
+        quad_pixel<C, SHADOWED>(v, n, pix, lb, le, image, fi);
 }
 
 // The two-pass shape of deferred_adjoint_kernel: a capped grid that strides over the pixels; pass 1 stores the texel gradients;
 // pass 2 loops over the quads on the outside with fifteen fp64 partials per lane, summed across the wave, across the four waves
 // through LDS, and the block writes ONE row of the slab: [quads of the image][15].  No atomics, a fixed order.
-template <int C>
+template <int C, bool SHADOWED>
 __global__ void __launch_bounds__(256, 2) deferred_quad_adjoint_kernel(const float *__restrict__ g, const float *__restrict__ quads,
                                                                        const int *__restrict__ type, const int *__restrict__ range,
                                                                        int height, int width, int aa,
                                                                        const float *__restrict__ d_image, float *__restrict__ d_g,
-                                                                       double *__restrict__ slab, int slab_stride) {
+                                                                       double *__restrict__ slab, int slab_stride,
+                                                                       const float *__restrict__ factors,
+                                                                       const int *__restrict__ pair_base) {
     const View v{g, quads, type, range, height, width, aa};
     const int n = blockIdx.y, pixels = v.height * v.width;
     const int lb = v.range[2 * n], le = v.range[2 * n + 1];
     const int first = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+    const float *fi = SHADOWED ? image_factors(v, factors, pair_base, n) : nullptr;
     for (int pix = first; pix < pixels; pix += step)
-        quad_adjoint_texels<C>(v, n, pix, lb, le, d_image, d_g);
+        quad_adjoint_texels<C, SHADOWED>(v, n, pix, lb, le, d_image, d_g, fi);
     __shared__ double wave_part[4][kQuadGrads];
     double *row = slab + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * slab_stride;
     for (int l = lb; l < le; ++l) {
         double part[kQuadGrads];
         for (int k = 0; k < kQuadGrads; ++k) part[k] = 0.0;
         for (int pix = first; pix < pixels; pix += step)
-            quad_adjoint_params<C>(v, n, pix, l, d_image, part);
+            quad_adjoint_params<C, SHADOWED>(v, n, pix, l, d_image, part, SHADOWED ? fi + factor_at(v, l - lb, 0, 0, 0, 0) : nullptr);
         for (int k = 0; k < kQuadGrads; ++k) part[k] = wave_sum(part[k]);           // every lane is active here
         if ((threadIdx.x & 63) == 0)
             for (int k = 0; k < kQuadGrads; ++k) wave_part[threadIdx.x >> 6][k] = part[k];
@@ -392,23 +428,27 @@ __global__ void __launch_bounds__(256) deferred_quad_fold_kernel(const double *_
 #endif
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-template <int C>
-inline void quad_impl(const rdr_deferred_desc &d, const View &v, float *image) {
+// `factors` and `pair_base` (SHADOWED): see the kernels; in the harness pair_base is host memory
+template <int C, bool SHADOWED = false>
+inline void quad_impl(const rdr_deferred_desc &d, const View &v, float *image, const float *factors = nullptr,
+                      const int *pair_base = nullptr) {
     const int pixels = d.height * d.width;
 #if !defined(RDR_HOSTSIM)
     const dim3 grid((pixels + 255) / 256, d.num_images);
-    hipLaunchKernelGGL((deferred_quad_kernel<C>), grid, dim3(256), 0, exec::ctx().stream, v.g, v.params, v.type, v.range, v.height,
-                       v.width, v.aa, image);
+    hipLaunchKernelGGL((deferred_quad_kernel<C, SHADOWED>), grid, dim3(256), 0, exec::ctx().stream, v.g, v.params, v.type, v.range,
+                       v.height, v.width, v.aa, image, factors, pair_base);
     exec::check(hipGetLastError(), "deferred_quad launch");
 #else
     for (int n = 0; n < d.num_images; ++n)
         for (int pix = 0; pix < pixels; ++pix)
-            quad_pixel<C>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], image);
+            quad_pixel<C, SHADOWED>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], image,
+                                    SHADOWED ? image_factors(v, factors, pair_base, n) : nullptr);
 #endif
 }
 
-template <int C>
-inline void quad_adjoint_impl(const rdr_deferred_desc &d, const View &v, const float *d_image, float *d_g, float *d_quads) {
+template <int C, bool SHADOWED = false>
+inline void quad_adjoint_impl(const rdr_deferred_desc &d, const View &v, const float *d_image, float *d_g, float *d_quads,
+                              const float *factors = nullptr, const int *pair_base = nullptr) {
     const int pixels = d.height * d.width;
 #if !defined(RDR_HOSTSIM)
     int per_image = (pixels + 255) / 256;
@@ -422,8 +462,8 @@ inline void quad_adjoint_impl(const rdr_deferred_desc &d, const View &v, const f
     const int slab_stride = longest * kQuadGrads;
     Arena arena;
     double *slab = arena.get<double>((size_t)per_image * d.num_images * slab_stride);
-    hipLaunchKernelGGL((deferred_quad_adjoint_kernel<C>), dim3(per_image, d.num_images), dim3(256), 0, exec::ctx().stream, v.g,
-                       v.params, v.type, v.range, v.height, v.width, v.aa, d_image, d_g, slab, slab_stride);
+    hipLaunchKernelGGL((deferred_quad_adjoint_kernel<C, SHADOWED>), dim3(per_image, d.num_images), dim3(256), 0, exec::ctx().stream,
+                       v.g, v.params, v.type, v.range, v.height, v.width, v.aa, d_image, d_g, slab, slab_stride, factors, pair_base);
     exec::check(hipGetLastError(), "deferred_quad_adjoint launch");
     if (d.num_lights > 0) {
         hipLaunchKernelGGL(deferred_quad_fold_kernel, dim3(d.num_lights), dim3(256), 0, exec::ctx().stream, slab, slab_stride,
@@ -434,13 +474,16 @@ inline void quad_adjoint_impl(const rdr_deferred_desc &d, const View &v, const f
 #else
     for (int n = 0; n < d.num_images; ++n)
         for (int pix = 0; pix < pixels; ++pix)
-            quad_adjoint_texels<C>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], d_image, d_g);
+            quad_adjoint_texels<C, SHADOWED>(v, n, pix, v.range[2 * n], v.range[2 * n + 1], d_image, d_g,
+                                             SHADOWED ? image_factors(v, factors, pair_base, n) : nullptr);
     for (int l = 0; l < d.num_lights; ++l) {
         double part[kQuadGrads] = {0};
         for (int n = 0; n < d.num_images; ++n) {
             if (l < v.range[2 * n] || l >= v.range[2 * n + 1]) continue;
             for (int pix = 0; pix < pixels; ++pix)
-                quad_adjoint_params<C>(v, n, pix, l, d_image, part);
+                quad_adjoint_params<C, SHADOWED>(v, n, pix, l, d_image, part,
+                                                 SHADOWED ? image_factors(v, factors, pair_base, n) +
+                                                            factor_at(v, l - v.range[2 * n], 0, 0, 0, 0) : nullptr);
         }
         for (int k = 0; k < kQuadGrads; ++k) d_quads[l * kQuadFloats + k] = (float)part[k];
         d_quads[l * kQuadFloats + kQuadGrads] = 0.f;

@@ -528,6 +528,27 @@ def deferred_quad_backward(g_buffer, quads, d_image, d_g_buffer, d_quads, num_im
           _ptr(d_image), _ptr(d_g_buffer), _ptr(d_quads), on=(use_gpu, gpu_index))
 
 
+def deferred_quad_shadowed(g_buffer, quads, factors, image, num_images, height, width, aa_samples, alpha, two_sided,
+                           image_quad_ranges, use_gpu, gpu_index, occluders, visibility, shadow_rays):
+    """Not in the reference: rdr_deferred_quad_shadowed (csrc/deferred_quad_shadow_abi.h): deferred_quad with every (quad, texel)
+    term scaled by a visibility factor from `shadow_rays` (1 .. 32) any-hit rays over `occluders`, N Scenes (None: that image
+    is not shadowed).  `visibility`: int_ptr to [pairs, H * aa, W * aa] 32-bit words, `factors`: float_ptr to as many floats;
+    every one of both is written (pairs: the sum of the images' range lengths)."""
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, two_sided, image_quad_ranges, use_gpu, gpu_index,
+                              occluders=occluders, visibility=visibility)
+    _call(_capi.lib(), 'deferred_quad_shadowed', 'rdr_deferred_quad_shadowed', C.byref(d), _ptr(g_buffer), _ptr(quads),
+          int(shadow_rays), _ptr(factors), _ptr(image), on=(use_gpu, gpu_index))
+
+
+def deferred_quad_shadowed_backward(g_buffer, quads, factors, d_image, d_g_buffer, d_quads, num_images, height, width, aa_samples,
+                                    alpha, two_sided, image_quad_ranges, use_gpu, gpu_index):
+    """Not in the reference: rdr_deferred_quad_shadowed_backward; writes every element of d_g_buffer and d_quads.  `factors`:
+    what the forward call wrote, held constant (no scene is needed)."""
+    d, _keep = _deferred_desc(num_images, height, width, aa_samples, alpha, two_sided, image_quad_ranges, use_gpu, gpu_index)
+    _call(_capi.lib(), 'deferred_quad_shadowed_backward', 'rdr_deferred_quad_shadowed_backward', C.byref(d), _ptr(g_buffer),
+          _ptr(quads), _ptr(factors), _ptr(d_image), _ptr(d_g_buffer), _ptr(d_quads), on=(use_gpu, gpu_index))
+
+
 def mip_num_levels(height, width):
     """Not in the reference's module: rdr_mip_num_levels, min(ceil(log2(max(height, width))) + 1, 8)."""
     return int(_capi.lib().rdr_mip_num_levels(int(height), int(width)))

@@ -87,8 +87,23 @@ F / pi is the view factor; a quad that fills the hemisphere gives L * a.  The no
 stored).  Gradients reach p, n, a, the four corners and L; max(S, 0) passes half the gradient at S == 0, |S| passes sign(S), the
 conditions are constants.  A QuadLight never enters the ten-float light table: `render_deferred` shades the table lights as before
 and adds `deferred_quad` of the quads.  NOT done: quad lights are not shadowed by `shadows=True` (and do
-not count towards its 32 rows), are not dimmed by ambient occlusion and cast no specular highlight; the emitter's own surface,
-where it is in the G-buffer, is shaded like any other surface.
+not count towards its 32 rows; soft shadows are below), are not dimmed by ambient occlusion and cast no specular highlight; the
+emitter's own surface, where it is in the G-buffer, is shaded like any other surface.
+
+Soft shadows of the quad lights (`render_deferred(..., quad_shadow_rays=K)`, `deferred_quad(..., occluders=..., shadow_rays=K)`;
+`rdr_deferred_quad_shadowed`, csrc/deferred_quad_shadow.h): the ratio estimator of Heitz et al. 2018.  Per texel and quad, K points
+(1 .. 32) of the quad from a fixed table -- stratified in u, a radical inverse in v, jittered by the texel's place in a 4 x 4 block
+-- each with the weight of the unshadowed integrand and one any-hit ray over the occluder scene, with the shadow rays' offsets:
+
+    s = q0 + u (q1 - q0) + v (q3 - q0) + u v ((q2 - q1) - (q3 - q0)),  J the patch's area element at (u, v),  d = s - p
+    w = (d.nh) (-d.J) / (d.d)^2  (two_sided: |d.J|)                    the sample counts where d.nh > 0, the quad faces the texel
+    V = sum of w over the counting samples whose ray is not blocked / sum of w over the counting samples;  1 without any
+    L * (a / pi) * F * V
+
+F stays exact, so a penumbra carries no noise from the form factor, and where nothing is in the way V == 1 and the bits are the
+unshadowed call's.  V is a constant of the gradient: the backward call reads the saved factors and traces nothing.  The estimator
+is biased, and its fixed point set has an error that does not average out over a frame (DESIGN.md section 7 has the measurement).
+csrc/deferred_quad_shadow_abi.h states the rule in the order of the fp32 operations.
 """
 import random
 from typing import List, Optional, Union
@@ -194,8 +209,9 @@ class QuadLight(DeferredLight):
     perimeter order, `intensity` [3], the radiance.  It emits on the side of cross(v1 - v0, v3 - v0), or on both with
     `two_sided`; the quad is expected to be planar and convex.  Every texel gets the exact diffuse irradiance of the part above
     its horizon (the module docstring has the formula).  It is shaded by `deferred_quad` (`render_deferred` does so for the
-    QuadLights in its list) and never enters the light table: it casts no shadow, is not dimmed by ambient occlusion and casts
-    no specular highlight."""
+    QuadLights in its list) and never enters the light table: it is not shadowed by `shadows=True` (softly by
+    `quad_shadow_rays=K` / `deferred_quad(occluders=..., shadow_rays=K)`), is not dimmed by ambient occlusion and casts no
+    specular highlight."""
     light_type = None
 
     def __init__(self, vertices: torch.Tensor, intensity: torch.Tensor, two_sided: bool = False):
@@ -661,15 +677,112 @@ class DeferredQuad(torch.autograd.Function):
         return d_g, d_table.to(ctx.quads_device), None, None, None, None, None
 
 
-def deferred_quad(g_buffer, lights, alpha=False, aa_samples=1, backend=None):
+class DeferredQuadShadowed(torch.autograd.Function):
+    """apply(g_buffer, quads, two_sided, image_quad_ranges, aa_samples, alpha, backend, occluders, shadow_rays[, factors])
+    -> (image [N, H, W, 3], words [P, H * aa, W * aa] int32, factors [P, H * aa, W * aa] fp32): DeferredQuad with soft shadows.
+    `occluders`: N `backend.Scene` (None: that image is not shadowed); `shadow_rays`: K in 1 .. 32 any-hit rays per texel and
+    quad towards fixed stratified points of the quad.  Each (quad, texel) term is multiplied by the factor
+    V = sum_k w_k vis_k / sum_k w_k (the module docstring; csrc/deferred_quad_shadow_abi.h has the rule); P is the sum of the
+    images' range lengths, and the pair of quad l of image n is (the earlier images' lengths) + l - begin_n.  Bit k of a word:
+    sample k does not count or its ray was not blocked.  `factors` (optional): the [P, H * aa, W * aa] fp32 tensor the factors
+    are written into.  The factors are saved for the backward call, which traces nothing and holds them constant; words and
+    factors carry no gradient.  Under create_graph=True the backward call raises."""
+
+    @staticmethod
+    def forward(ctx, g_buffer, quads, two_sided, image_quad_ranges, aa_samples, alpha, backend=None, occluders=None,
+                shadow_rays=0, factors=None):
+        rd = backend or _default_backend
+        two_sided = tuple(int(t) for t in two_sided)
+        image_quad_ranges = tuple((int(b), int(e)) for b, e in image_quad_ranges)
+        aa_samples, alpha, shadow_rays = int(aa_samples), bool(alpha), int(shadow_rays)
+        channels = 9 + int(alpha)
+        if g_buffer.dim() != 4 or g_buffer.shape[3] != channels:
+            raise RuntimeError('DeferredQuadShadowed: the G-buffer must be [N, H * aa, W * aa, %d], got %s'
+                               % (channels, tuple(g_buffer.shape)))
+        n, hg, wg = int(g_buffer.shape[0]), int(g_buffer.shape[1]), int(g_buffer.shape[2])
+        if aa_samples < 1 or hg % aa_samples != 0 or wg % aa_samples != 0 or n == 0 or hg == 0 or wg == 0:
+            raise RuntimeError('DeferredQuadShadowed: a G-buffer of %d x %d x %d does not divide into aa_samples = %d blocks'
+                               % (n, hg, wg, aa_samples))
+        if tuple(quads.shape) != (len(two_sided), _QUAD_FLOATS):
+            raise RuntimeError('DeferredQuadShadowed: quads must be [%d, %d], got %s'
+                               % (len(two_sided), _QUAD_FLOATS, tuple(quads.shape)))
+        if len(image_quad_ranges) != n:
+            raise RuntimeError('DeferredQuadShadowed: %d quad ranges for %d images' % (len(image_quad_ranges), n))
+        if g_buffer.dtype != torch.float32 or quads.dtype != torch.float32:
+            raise RuntimeError('DeferredQuadShadowed: fp32 tensors only')
+        if occluders is None or len(occluders) != n:
+            raise RuntimeError('DeferredQuadShadowed: occluders must be %d scenes (None: that image is not shadowed), got %s'
+                               % (n, 'None' if occluders is None else '%d' % len(occluders)))
+        if shadow_rays < 1 or shadow_rays > 32:
+            raise RuntimeError('DeferredQuadShadowed: shadow_rays must be 1 .. 32, got %d' % shadow_rays)
+        device = g_buffer.device
+        pairs = sum(max(e - b, 0) for b, e in image_quad_ranges)
+        if factors is not None and (tuple(factors.shape) != (pairs, hg, wg) or factors.dtype != torch.float32 or
+                                    factors.device != device or not factors.is_contiguous()):
+            raise RuntimeError('DeferredQuadShadowed: factors must be a contiguous [%d, %d, %d] fp32 tensor on %s, got %s'
+                               % (pairs, hg, wg, device, tuple(factors.shape)))
+        use_gpu, index = place(device)
+        g = _aligned(g_buffer.detach(), alpha)
+        table = quads.detach().to(device).contiguous()
+        h, w = hg // aa_samples, wg // aa_samples
+        image = torch.empty(n, h, w, 3, dtype=torch.float32, device=device)
+        words = torch.empty(pairs, hg, wg, dtype=torch.int32, device=device)           # every word and factor is written
+        if factors is None:
+            factors = torch.empty(pairs, hg, wg, dtype=torch.float32, device=device)
+        # (a call without a pair still hands the library two buffers it can name: four bytes each, of which nothing is returned)
+        spare = torch.empty(2, dtype=torch.int32, device=device) if pairs == 0 else None
+        geometry = (n, h, w, aa_samples, alpha, two_sided, image_quad_ranges, use_gpu, index)
+        ctx.rd, ctx.geometry, ctx.quads_device = rd, geometry, quads.device
+        rd.deferred_quad_shadowed(ptr(rd, g), ptr(rd, table), rd.float_ptr((factors if spare is None else spare[1:]).data_ptr()),
+                                  ptr(rd, image), *geometry, occluders=tuple(occluders),
+                                  visibility=rd.int_ptr((words if spare is None else spare).data_ptr()), shadow_rays=shadow_rays)
+        ctx.save_for_backward(g, table, factors)
+        ctx.mark_non_differentiable(words, factors)
+        return image, words, factors
+
+    @staticmethod
+    def backward(ctx, grad_img, grad_words, grad_factors):
+        first_order_only('DeferredQuadShadowed')
+        rd, geometry = ctx.rd, ctx.geometry
+        g, table, factors = ctx.saved_tensors
+        grad_img = upstream(grad_img, g.device)
+        assert torch.isfinite(grad_img).all()
+        d_g, d_table = torch.empty_like(g), torch.empty_like(table)
+        if factors.shape[0] == 0:              # (no pair: as in forward)
+            factors = torch.ones(1, dtype=torch.float32, device=g.device)
+        rd.deferred_quad_shadowed_backward(ptr(rd, g), ptr(rd, table), ptr(rd, factors), ptr(rd, grad_img), ptr(rd, d_g),
+                                           ptr(rd, d_table), *geometry)
+        return d_g, d_table.to(ctx.quads_device), None, None, None, None, None, None, None, None
+
+
+def deferred_quad(g_buffer, lights, alpha=False, aa_samples=1, backend=None, occluders=None, shadow_rays=0,
+                  return_visibility=False):
     """The light of QuadLights on a stack of G-buffers [N, H * aa, W * aa, 9 + alpha] -> [N, H, W, 3], to be added to the colour
     channels of `deferred_shade`'s image.  `lights`: one list of QuadLight shared by the N images, or N lists (an empty one is
-    fine).  The lights are exact, unshadowed area emitters (the module docstring has the formula and what is left out);
+    fine).  The lights are exact area emitters (the module docstring has the formula and what is left out);
     gradients reach position, normal and albedo, and the corners and radiance of every QuadLight -- through `quad_light`, its
-    position, look_at and size."""
+    position, look_at and size.
+    Soft shadows: `occluders`, one `occluder_scene(...)` for all images or a list of N of them (None: that image is not
+    shadowed), together with `shadow_rays`, K in 1 .. 32 any-hit rays per texel and quad; each quad's light on a texel is
+    multiplied by the weighted fraction of K fixed points of the quad that the texel sees.  One without the other raises.  The
+    factors are held constant by the gradient.  `return_visibility`: also (words, factors), [P, H * aa, W * aa] int32 and fp32,
+    one plane per (image, quad) pair in the order of the images and of each image's list.  With the defaults: the launches and
+    the bits of the call without these arguments."""
     n = int(g_buffer.shape[0])
+    shadow_rays = int(shadow_rays)
+    if occluders is None and shadow_rays == 0 and not return_visibility:
+        quads, flags, ranges = _quad_table(lights, n, g_buffer.device)
+        return DeferredQuad.apply(g_buffer, quads, tuple(flags), tuple(ranges), aa_samples, alpha, backend)
+    if occluders is None:
+        raise RuntimeError('deferred_quad: shadow_rays = %d (or return_visibility) needs occluders to trace the rays over'
+                           % shadow_rays)
+    if shadow_rays < 1 or shadow_rays > 32:
+        raise RuntimeError('deferred_quad: with occluders, shadow_rays must be 1 .. 32 rays per texel and quad, got %d' % shadow_rays)
     quads, flags, ranges = _quad_table(lights, n, g_buffer.device)
-    return DeferredQuad.apply(g_buffer, quads, tuple(flags), tuple(ranges), aa_samples, alpha, backend)
+    scenes = _per_image_scenes(occluders, n)                                              # (`occluders` lives through the call)
+    image, words, factors = DeferredQuadShadowed.apply(g_buffer, quads, tuple(flags), tuple(ranges), aa_samples, alpha, backend,
+                                                       scenes, shadow_rays)
+    return (image, (words, factors)) if return_visibility else image
 
 
 def _default_device(device):
@@ -718,9 +831,14 @@ def _eye_of(camera, backend):
     return torch.as_tensor(camera.position).reshape(3)
 
 
-def _add_quads(images, g_buffer, quad_lights, alpha, aa_samples, backend):
-    """images + deferred_quad of the QuadLights on the same G-buffer; the alpha channel is left as it is"""
-    light = deferred_quad(g_buffer, quad_lights, alpha=alpha, aa_samples=aa_samples, backend=backend)
+def _add_quads(images, g_buffer, quad_lights, alpha, aa_samples, backend, occluders=None, shadow_rays=0):
+    """images + deferred_quad of the QuadLights on the same G-buffer (softly shadowed by `occluders` when `shadow_rays` > 0); the
+    alpha channel is left as it is"""
+    if shadow_rays:
+        light = deferred_quad(g_buffer, quad_lights, alpha=alpha, aa_samples=aa_samples, backend=backend, occluders=occluders,
+                              shadow_rays=shadow_rays)
+    else:
+        light = deferred_quad(g_buffer, quad_lights, alpha=alpha, aa_samples=aa_samples, backend=backend)
     if alpha:
         light = torch.cat([light, torch.zeros_like(light[..., :1])], dim=-1)
     return images + light
@@ -729,7 +847,7 @@ def _add_quads(images, g_buffer, quad_lights, alpha, aa_samples, backend):
 def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = False, aa_samples: int = 2, seed=None,
                     sample_pixel_center: bool = False, use_primary_edge_sampling: bool = True,
                     device: Optional[torch.device] = None, backend=None, shadows: bool = False, ambient_occlusion: int = 0,
-                    ao_radius: float = float('inf'), specular: bool = False):
+                    ao_radius: float = float('inf'), specular: bool = False, quad_shadow_rays: int = 0):
     """Deferred rendering: Lambertian shading of the G-buffer by `lights` and, with `specular`, the specular lobe on top.
 
     scene: a Scene -> [H, W, 3 | 4]; a list of N scenes of one resolution -> [N, H, W, 3 | 4], shaded in one launch.
@@ -756,7 +874,13 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
     are shaded exactly as without them, the quads by `deferred_quad` on the same G-buffer, and the sum is returned (alpha is the
     diffuse pass's).  Quad lights are NOT shadowed by `shadows` and do not count towards its 32 rows, are NOT dimmed by
     `ambient_occlusion` and cast NO specular highlight; the emitter's own surface, where the scene holds it, is shaded like any
-    other surface.  Without a QuadLight in `lights`: the same launches and the same bits as before there were any."""
+    other surface.  Without a QuadLight in `lights`: the same launches and the same bits as before there were any.
+    `quad_shadow_rays` (redner_amd extension), independent of `shadows`: K in 1 .. 32 any-hit rays per texel and QuadLight over
+    the triangles of its scene, towards K fixed stratified points of the quad; the quad's exact light on the texel is multiplied
+    by the weighted fraction of the points the texel sees (`deferred_quad(..., occluders=..., shadow_rays=K)`): SOFT shadows
+    with a penumbra, whose only error is in that fraction.  The rays end short of the quad, so the emitter's own mesh in the
+    scene does not block them.  Held constant by the gradient, like visibility.  The occluder scene is the one `shadows` and
+    `ambient_occlusion` use, built once.  0: the same launches and the same bits as without the argument."""
     backend = backend or _default_backend
     device = _default_device(device)
     aa_samples = int(aa_samples)
@@ -777,14 +901,19 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
                                                device, backend) for sc, se in zip(scenes, seeds)]
     g_buffer = g_buffers[0].unsqueeze(0) if single else torch.stack(g_buffers)
     # (the occluder scenes live until the shade call has returned)
-    ambient_occlusion = int(ambient_occlusion)
-    built = [occluder_scene(sc, device=device, backend=backend) for sc in scenes] if shadows or ambient_occlusion else None
+    ambient_occlusion, quad_shadow_rays = int(ambient_occlusion), int(quad_shadow_rays)
+    if quad_shadow_rays < 0 or quad_shadow_rays > 32:
+        raise RuntimeError('render_deferred: quad_shadow_rays must be 0 (off) or 1 .. 32 rays per texel and QuadLight, got %d'
+                           % quad_shadow_rays)
+    quad_rays = quad_shadow_rays if quad_lights is not None else 0
+    built = [occluder_scene(sc, device=device, backend=backend) for sc in scenes] if shadows or ambient_occlusion or quad_rays \
+        else None
     if not specular:
         images = deferred_shade(g_buffer, lights, alpha=alpha, aa_samples=aa_samples, backend=backend,
                                 occluders=built if shadows else None, ambient_occlusion=ambient_occlusion, ao_radius=ao_radius,
                                 ao_occluders=built if ambient_occlusion else None)
         if quad_lights is not None:
-            images = _add_quads(images, g_buffer, quad_lights, alpha, aa_samples, backend)
+            images = _add_quads(images, g_buffer, quad_lights, alpha, aa_samples, backend, built, quad_rays)
         return images[0] if single else images
     # the diffuse part exactly as above on its own channels (asking for the words when there are shadows), then the lobe
     diffuse_channels = 9 + int(bool(alpha))
@@ -800,7 +929,7 @@ def render_deferred(scene: Union[Scene, List[Scene]], lights, alpha: bool = Fals
         highlights = torch.cat([highlights, torch.zeros_like(highlights[..., :1])], dim=-1)
     images = images + highlights
     if quad_lights is not None:
-        images = _add_quads(images, g, quad_lights, alpha, aa_samples, backend)
+        images = _add_quads(images, g, quad_lights, alpha, aa_samples, backend, built, quad_rays)
     return images[0] if single else images
 
 
